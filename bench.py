@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Headline benchmark of the MI355X-native NRMS training path.
 
-    python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4|c5|c5h50]
+    python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4|c5|c5h50] [--dump-outputs DIR]
+
+K is the number of timed steps in all (dealt over --repeats windows; `ms_per_step` is the median window's).  With
+--dump-outputs, what the final timed step computed is written as DIR/<name>.npy (see dump_outputs()).
 
 N > 1: either launched by ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`` (one rank per
 GPU over RCCL), or started directly, in which case it re-launches itself that way.  With fewer visible GPUs than ranks
@@ -219,28 +222,100 @@ def step_flops(c):
     return f
 
 
+CLOCK_WARM_S = 0.2
+
+
+def warm_clocks(sync, device, seconds=CLOCK_WARM_S):
+    """Keep the chip busy for `seconds` with the project's exact-fp32 GEMM (the step's dominant kind of work) on scratch
+    operands that no model state shares, so that the timed windows start at steady clocks (the chip needs ~50 ms of
+    sustained load after an idle gap: see time_kernel) however few steps they hold."""
+    from ebrec import _hip
+
+    M, N, K = 8192, 1200, 1024
+    g = torch.Generator(device=device).manual_seed(0)  # (not the global generator: nothing seeded later sees these draws)
+    a, b = torch.rand(M, K, device=device, generator=g), torch.rand(K, N, device=device, generator=g)
+    c = torch.empty(M, N, device=device)
+    nbytes = int(_hip.lib().ebn_gemm_prec_workspace_bytes(M, N, K, 0))
+    ws = torch.empty(nbytes // 4 + 64, device=device)
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(16):
+            _hip.call("ebn_gemm_f32_prec", 0, 0, M, N, K, ctypes.c_float(1.0), _hip.ptr(a), K, _hip.ptr(b), N, ctypes.c_float(0.0),
+                      _hip.ptr(c), N, _hip.ptr(ws), nbytes, 0, _hip.stream_handle())
+        torch.cuda.synchronize(device)
+    del a, b, c, ws
+    sync()
+
+
 def timed_repeats(step_fn, args, sync, world, device):
-    """W untimed warm-up steps, then R repeats of EXACTLY K steps, each bracketed by barrier + synchronize on both sides;
-    per repeat the MAX over ranks.  Returns the R wall times (seconds)."""
+    """W untimed warm-up steps, then EXACTLY K timed steps (K = args.steps) dealt over R = min(args.repeats, K) back-to-back
+    windows whose sizes differ by at most one: barrier + synchronize before the first window and after the last, a HIP
+    event on the launch stream at every window boundary; per window the MAX over ranks.  step_fn(k, last) runs step k;
+    `last` is True for the final timed step only.  Returns the windows' (seconds, steps) and what the final timed step
+    returned."""
     k = 0
     for _ in range(args.warmup):
-        step_fn(k)
+        step_fn(k, False)
         k += 1
-    times = []
-    for _ in range(args.repeats):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step_fn(k)
+    warm_clocks(sync, device)
+    n_win = max(1, min(args.repeats, args.steps))
+    sizes = [args.steps // n_win + (1 if i < args.steps % n_win else 0) for i in range(n_win)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(n_win + 1)]
+    out = None
+    sync()
+    ev[0].record()
+    for i, n in enumerate(sizes):
+        for _ in range(n):
+            out = step_fn(k, k == args.warmup + args.steps - 1)
             k += 1
-        sync()
-        dt = time.perf_counter() - t0
-        if world > 1 or dist.is_initialized():  # (a one-rank group under --force-dist: the same collective, an identity)
-            t = torch.tensor([dt], device=device, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-        times.append(dt)
-    return times
+        ev[i + 1].record()
+    sync()
+    dts = [ev[i].elapsed_time(ev[i + 1]) * 1e-3 for i in range(n_win)]
+    if world > 1 or dist.is_initialized():  # (a one-rank group under --force-dist: the same collective, an identity)
+        t = torch.tensor(dts, device=device, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dts = [float(v) for v in t.cpu()]
+    return list(zip(dts, sizes)), out
+
+
+def window_ms(windows):
+    """milliseconds per step of each timed window, in run order"""
+    return [dt / n * 1e3 for dt, n in windows]
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_TABLE_ROWS = 8192
+
+
+def dump_outputs(out_dir, eng, last):
+    """--dump-outputs: what the timed path computed in its final timed step, as DIR/<name>.npy -- the step's returns (`loss`,
+    the click probabilities `probs`, the `labels` as staged), every dense parameter after the step's Adam update
+    (`param.<name>`), the batch-norm moving statistics of a news-encoder MLP and, with a trainable table, a fixed sample
+    of its rows (`table.sample`, at the row numbers `table.rows`: the same DUMP_TABLE_ROWS rows in every run).  With a
+    row-sharded table the process dumping (rank 0) holds only its shard, so the sample is of rank 0's shard and
+    `table.rows` are row numbers within that shard, not global ids.  float32, the row numbers float64.  Inputs and weights are seeded, so two builds run with the same arguments compare array for
+    array."""
+    loss, probs, labels = last
+    arrays = {"loss": loss, "probs": probs, "labels": labels}
+    for name in eng.params.shapes:
+        arrays[f"param.{name}"] = eng.params.view(name)
+    mlp = getattr(eng, "mlp", None)
+    if mlp is not None:
+        for l in range(len(mlp.units)):
+            arrays[f"bn{l}.moving_mean"], arrays[f"bn{l}.moving_variance"] = mlp.bn_mean[l], mlp.bn_var[l]
+    if getattr(eng, "train_embedding", False):
+        V = eng.table.shape[0]
+        rows = np.sort(np.random.default_rng(0).choice(V, min(V, DUMP_TABLE_ROWS), replace=False))
+        arrays["table.rows"] = rows.astype(np.float64)
+        arrays["table.sample"] = eng.table[torch.from_numpy(rows).to(eng.table.device)]
+    host = {k: (v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    for name, a in host.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(Path(out_dir, f"{name}.npy"), a)
 
 
 def launches_of_one_step(eng, step_fn, sync):
@@ -358,7 +433,7 @@ def fit_loop_leg(model, c, n_steps=100):
 def split_precision_leg(c, make_model, batches, args, sync, device, exact_ms):
     """The opt-in second precision of the projection GEMMs (profiles/HISTORY.md section 4a: every fp32 operand split exactly into three bf16 values, six
     bf16 MFMA cross products, fp32 accumulate), timed in the SAME run as the exact-fp32 headline so that the driver's line carries
-    it: K steps x R repeats of the same batches on a second engine, and the accuracy evidence next to it -- the max abs error of
+    it: the same K timed steps of the same batches on a second engine, and the accuracy evidence next to it -- the max abs error of
     the Q|K|V projection of one real step (this run's gathered, dropped-out X and this model's Wqkv) against float64, for the
     split GEMM and for the exact-fp32 GEMM on the same operands."""
     from ebrec import _hip
@@ -366,9 +441,9 @@ def split_precision_leg(c, make_model, batches, args, sync, device, exact_ms):
     model = make_model("split")
     eng = model._engine
     eng.enable_graphs(not args.no_graph)
-    times = timed_repeats(lambda k: eng.train_step(*batches[k % len(batches)]), argparse.Namespace(warmup=args.warmup, repeats=args.repeats, steps=args.steps),
-                          sync, 1, device)
-    ms = float(np.median([t / args.steps * 1e3 for t in times]))
+    times, _ = timed_repeats(lambda k, _last: eng.train_step(*batches[k % len(batches)]),
+                             argparse.Namespace(warmup=args.warmup, repeats=args.repeats, steps=args.steps), sync, 1, device)
+    ms = float(np.median(window_ms(times)))
     # accuracy of the projection on a sample of real operands: 2048 token rows of an eager exact-precision gather
     ex = make_model("exact")._engine
     ex.train_step(*batches[0])
@@ -386,7 +461,7 @@ def split_precision_leg(c, make_model, batches, args, sync, device, exact_ms):
         errs[name] = float((C.double() - ref).abs().max())
     del model, ex
     torch.cuda.empty_cache()
-    return {"value": c["B"] / (ms * 1e-3), "unit": "impressions/s", "ms_per_step": ms, "ms_per_step_repeats": [t / args.steps * 1e3 for t in times],
+    return {"value": c["B"] / (ms * 1e-3), "unit": "impressions/s", "ms_per_step": ms, "ms_per_step_repeats": window_ms(times),
             "speedup_vs_exact": exact_ms / ms, "dtype": "f32 (bf16x6 split, fp32 accumulate)",
             "projection_max_abs_err_vs_fp64": errs, "projection_ref_max_abs": float(ref.abs().max()),
             "what": "OPT-IN second precision, never the headline `value`: the news encoder's projection GEMMs as six bf16 MFMA products of "
@@ -471,15 +546,15 @@ def static_traffic(config):
         time.strftime("%Y-%m-%d", time.gmtime(tf.stat().st_mtime)) + "; NOT measured in this run)"
 
 
-def timing_fields(times, args, world, per_gpu_batch):
-    """value / ms_per_step from the MEDIAN repeat; spread alongside."""
-    ms = sorted(t / args.steps * 1e3 for t in times)
+def timing_fields(windows, args, world, per_gpu_batch):
+    """value / ms_per_step from the MEDIAN window; spread alongside."""
+    ms = sorted(window_ms(windows))
     med = float(np.median(ms))
     return {"value": world * per_gpu_batch / (med * 1e-3), "ms_per_step": med, "ms_per_step_min": ms[0], "ms_per_step_max": ms[-1],
-            "repeats": len(ms), "ms_per_step_repeats": [t / args.steps * 1e3 for t in times],
-            "timing": f"median of {len(ms)} repeats of {args.steps} steps each (barrier + synchronize around every repeat, max over ranks); "
-                      "`ms_per_step_repeats` lists them in run order -- the first one starts on a chip that has just idled (clock ramp, "
-                      "~50 ms) and is the slow one the median sets aside, not an average over it"}
+            "repeats": len(ms), "ms_per_step_repeats": window_ms(windows),
+            "timing": f"{args.steps} timed steps after {args.warmup} warm-up steps and {CLOCK_WARM_S} s of clock warm-up GEMMs, dealt over {len(ms)} back-to-back "
+                      f"windows of {'/'.join(str(n) for _, n in windows)} steps (HIP events on the launch stream at the window boundaries, max over ranks); "
+                      "ms_per_step is the median window's; `ms_per_step_repeats` lists the windows in run order"}
 
 
 def dist_fields(world, backend, n_dev, forced=False):
@@ -529,7 +604,9 @@ def bench_docvec(args, c, world, rank, device, sync, dfields, multi=False):
         sync()
         return
     eng.enable_graphs(not args.no_graph)
-    times = timed_repeats(lambda k: eng.train_step(*batches[k % 8], indexed=True), args, sync, world, device)
+    times, last = timed_repeats(lambda k, last: eng.train_step(*batches[k % 8], indexed=True, return_probs=last), args, sync, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, last)
     n_launches = launches_of_one_step(eng, lambda: eng.train_step(*batches[0], indexed=True), sync)
     # kernel-level rooflines on the step's own buffers: the document-vector gather (HBM) and the time-dominant launch of the step,
     # the grouped weight-gradient product of all Dense kernels (MFMA)
@@ -827,9 +904,10 @@ def self_launch(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed loop of --steps steps is run this many times; the median is reported")
+    ap.add_argument("--steps", type=int, default=50, help="timed steps in all (after the warm-up)")
+    ap.add_argument("--warmup", type=int, default=10, help="untimed warm-up steps")
+    ap.add_argument("--repeats", type=int, default=5, help="the --steps timed steps are dealt over this many consecutive windows; the median "
+                                                            "window's ms per step is reported")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
     ap.add_argument("--ids", default="uniform", choices=["uniform", "zipf"],
@@ -870,9 +948,14 @@ def main():
                     help="test hook: this rank skips its collectives in the timed region (its peers then wait for it forever): the hang "
                          "watchdog must turn that into exit code 124 within EBN_COLLECTIVE_TIMEOUT_S")
     ap.add_argument("--probe-launches", type=int, default=24, help="internal: launches of each roofline kernel in --kernel-probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the final timed step computed (loss, probabilities, labels, the updated "
+                         "parameters, a fixed sample of a trainable table's rows) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--kernel-probe", action="store_true", help="internal: launch the two roofline kernels a few times on the step's "
                                                                 "buffers and exit (what probe_kernels() wraps rocprofv3 around)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -973,8 +1056,10 @@ def main():
         eng.skip_collectives = True
         if eng.exchange is not None:
             eng.exchange.skip = True
-    phase(f"{args.config}: warm-up + timed region ({args.warmup} + {args.repeats} x {args.steps} steps)")
-    times = timed_repeats(lambda k: eng.train_step(*batches[k % len(batches)]), args, sync, world, device)
+    phase(f"{args.config}: warm-up + timed region ({args.warmup} + {args.steps} steps)")
+    times, last = timed_repeats(lambda k, last: eng.train_step(*batches[k % len(batches)], return_probs=last), args, sync, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, last)
     n_launches = launches_of_one_step(eng, lambda: eng.train_step(*batches[0]), sync) if not multi else None
     # Kernel-level rooflines: the Q|K|V projection GEMM and the embedding gather of THIS step (same buffers, same
     # arguments), each captured into a hipGraph of 10 launches and timed with HIP events on the launch stream.
@@ -995,14 +1080,14 @@ def main():
             eng._graphs.clear()  # the collectives are part of the captured step: re-capture without them
         if eng.exchange is not None:
             eng.exchange.skip = True
-        t_no = timed_repeats(lambda k: eng.train_step(*batches[k % len(batches)]), argparse.Namespace(warmup=2, repeats=max(args.repeats, 3), steps=args.steps),
-                             sync, world, device)
+        t_no, _ = timed_repeats(lambda k, _last: eng.train_step(*batches[k % len(batches)]),
+                                argparse.Namespace(warmup=2, repeats=max(args.repeats, 3), steps=args.steps), sync, world, device)
         eng.skip_collectives = False
         if eng.graph_collectives:
             eng._graphs.clear()
         if eng.exchange is not None:
             eng.exchange.skip = False
-        ms_no = float(np.median([t / args.steps * 1e3 for t in t_no]))
+        ms_no = float(np.median(window_ms(t_no)))
         comm = {"ms_per_step_without_collectives": ms_no, "overlap": bool(eng.overlap_collectives), "collectives_in_graph": bool(eng.graph_collectives), "graph_collectives_mode": args.graph_collectives}
     phase(f"{args.config}: closing flag check (a collective)")
     eng.check_oob()  # sticky device flags of the whole run (ids out of range, exchange overflow, accumulator range): raise, don't report
