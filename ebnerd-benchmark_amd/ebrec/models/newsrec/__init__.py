@@ -1,5 +1,5 @@
-"""MI355X-native NRMS / NRMSDocVec (NPA, LSTUR and NAML of the reference are out of scope)."""
-from .model_config import hparams_nrms, hparams_nrms_docvec, hparams_to_dict, print_hparams  # noqa: F401
+"""MI355X-native NRMS / NRMSDocVec / NPA (LSTUR and NAML of the reference are out of scope)."""
+from .model_config import hparams_npa, hparams_nrms, hparams_nrms_docvec, hparams_to_dict, print_hparams  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing model_config / dataloader must not need torch or a GPU
@@ -9,4 +9,7 @@ def __getattr__(name):  # lazy: importing model_config / dataloader must not nee
     if name == "NRMSDocVec":
         from .nrms_docvec import NRMSDocVec
         return NRMSDocVec
+    if name == "NPAModel":
+        from .npa import NPAModel
+        return NPAModel
     raise AttributeError(name)

@@ -54,7 +54,7 @@ def _full_batches(data) -> int:
     """number of leading batches of `data` that have the full batch size (all but possibly the last one)"""
     bs = getattr(data, "batch_size", None) or getattr(data, "bs", None)
     rows = getattr(data, "X", None)
-    rows = rows if rows is not None else getattr(data, "his", None)
+    rows = rows if rows is not None else getattr(data, "rows", None)
     if bs is None or rows is None:
         return len(data)
     return len(rows) // int(bs)
@@ -65,19 +65,20 @@ def _is_loader(x):
 
 
 class _ArrayBatches:
-    """(his, pred), y arrays sliced like a Keras Sequence."""
+    """A tuple of input arrays ((his, pred) for NRMS, (user, his, pred) for NPA) and y, sliced like a Keras Sequence."""
 
     def __init__(self, x, y, batch_size):
-        self.his, self.pred = x
+        self.xs = tuple(x)
+        self.rows = self.xs[0]
         self.y = y
         self.bs = int(batch_size or 32)
 
     def __len__(self):
-        return int(np.ceil(len(self.his) / self.bs))
+        return int(np.ceil(len(self.rows) / self.bs))
 
     def __getitem__(self, i):
         s = slice(i * self.bs, (i + 1) * self.bs)
-        return (self.his[s], self.pred[s]), (None if self.y is None else self.y[s])
+        return tuple(a[s] for a in self.xs), (None if self.y is None else self.y[s])
 
 
 class _Optimizer:
@@ -105,7 +106,8 @@ class _Variable(SimpleNamespace):
 
 
 class TrainModel:
-    """``NRMSModel.model``: inputs [his (B,H,T), pred (B,C,T)] -> softmax probabilities (B,C)."""
+    """``NRMSModel.model``: inputs [his (B,H,T), pred (B,C,T)] -> softmax probabilities (B,C); ``NPAModel.model``: inputs
+    [user (B,1), his, pred].  Batches are input tuples handed to the engine as they are."""
 
     cache_articles = True  # evaluate(): encode the loader's article matrix once (set False to force per-batch encoding)
 
@@ -246,13 +248,13 @@ class TrainModel:
                 except ValueError:  # not this engine's kind of matrix (token ids vs document vectors): host-gathered batches
                     indexed = False
             for step, idx in enumerate(order):
-                (his, pred), yb = data.index_batch(int(idx)) if indexed else data[int(idx)]
-                nb = len(his)
+                xb, yb = data.index_batch(int(idx)) if indexed else data[int(idx)]
+                nb = len(xb[0])
                 if want_auc:
-                    loss, probs, labels_dev = eng.train_step(his, pred, yb, return_probs=True, **({"indexed": True} if indexed else {}))
+                    loss, probs, labels_dev = eng.train_step(*xb, yb, return_probs=True, **({"indexed": True} if indexed else {}))
                     auc.update_device(labels_dev, probs)
                 else:
-                    loss = eng.train_step(his, pred, yb, **({"indexed": True} if indexed else {}))
+                    loss = eng.train_step(*xb, yb, **({"indexed": True} if indexed else {}))
                 loss_sum += loss * nb
                 n_rows += nb
                 for cb in cbs:
@@ -308,8 +310,9 @@ class TrainModel:
                     (his, pred), yb = data.index_batch(i)
                     loss, probs = eval_loss_from_news(eng, news_all, his, pred, yb)
                 else:
-                    (his, pred), yb = data[i]
-                    loss, probs = eng.eval_loss(his, pred, yb)
+                    xb, yb = data[i]
+                    his = xb[0]
+                    loss, probs = eng.eval_loss(*xb, yb)
                 loss_sum += loss * len(his)  # stays on the device: one host sync per evaluate(), not per batch
                 n_rows += len(his)
                 if auc is not None:
@@ -331,14 +334,13 @@ class TrainModel:
         data = x if _is_loader(x) else _ArrayBatches(x, None, batch_size)
         outs = []
         for i in range(len(data)):
-            (his, pred), _y = data[i]
-            probs, _ = self._engine.forward(his, pred, mode="softmax")
+            xb, _y = data[i]
+            probs, _ = self._engine.forward(*xb, mode="softmax")
             outs.append(probs.cpu().numpy())
         return np.concatenate(outs, axis=0) if outs else np.zeros((0, 0), np.float32)
 
     def __call__(self, inputs, training=False):
-        his, pred = inputs
-        return self._engine.forward(his, pred, mode="softmax")[0]
+        return self._engine.forward(*inputs, mode="softmax")[0]
 
 
 class ScorerModel:
@@ -368,17 +370,16 @@ class ScorerModel:
             return np.concatenate(outs, axis=0) if outs else np.zeros((0, 1), np.float32)
         for i in range(len(data)):
             if compact is not None:  # this repo's loaders: history rows are NOT materialised per candidate
-                his, cand, rows, _y = compact(i)
-                s = self._owner._score_compact(np.asarray(his), np.asarray(cand), np.asarray(rows))
+                *xs, _y = compact(i)  # (his, cand, rows) -- (user, his, cand, rows) for NPA
+                s = self._owner._score_compact(*(np.asarray(a) for a in xs))
             else:
-                (his, pred_one), _y = data[i]
-                s = self._owner._score_pairs(np.asarray(his), np.asarray(pred_one))
+                xb, _y = data[i]
+                s = self._owner._score_pairs(*(np.asarray(a) for a in xb))
             outs.append(s.cpu().numpy().reshape(-1, 1))
         return np.concatenate(outs, axis=0) if outs else np.zeros((0, 1), np.float32)
 
     def __call__(self, inputs, training=False):
-        his, pred_one = inputs
-        return self._owner._score_pairs(np.asarray(his), np.asarray(pred_one)).view(-1, 1)
+        return self._owner._score_pairs(*(np.asarray(a) for a in inputs)).view(-1, 1)
 
 
 class EncoderModel:

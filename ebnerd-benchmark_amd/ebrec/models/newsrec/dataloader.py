@@ -177,3 +177,47 @@ class NRMSDataLoader(NewsrecDataLoader):
 class NRMSDataLoaderPretransform(NRMSDataLoader):
     """reference dataloader.py:122-180: the whole frame is mapped up front (which NRMSDataLoader here
     does as well -- the class is kept so ``--nrms_loader NRMSDataLoaderPretransform`` keeps working)."""
+
+
+@dataclass
+class LSTURDataLoader(NRMSDataLoader):
+    """reference dataloader.py:183-263 ("NPA and LSTUR shares the same DataLoader"): the NRMS batches plus the user index of
+    every impression, ``user_id_mapping[user_id]`` (``unknown_user_value`` for users not in the mapping).
+
+      train mode   ((user_indexes (B,1), his (B,H,T), pred (B,C,T)), y (B,C))
+      eval mode    ((user_indexes (sum C_i,1), his (sum C_i,H,T), pred (sum C_i,1,T)), y (sum C_i,1))  -- user and history
+                   repeated once per candidate
+    """
+
+    user_id_mapping: dict = None
+    unknown_user_value: int = 0
+
+    def __post_init__(self):
+        super().__post_init__()
+        mapping = self.user_id_mapping or {}
+        get, unk = mapping.get, int(self.unknown_user_value)
+        users = self.X[self.user_col].tolist() if len(self.X) else []
+        self._users = np.fromiter((get(u, unk) for u in users), dtype=np.int64, count=len(users))
+
+    def _user_rows(self, lo, hi) -> np.ndarray:
+        return self._users[lo:hi]
+
+    def __getitem__(self, idx):
+        (his, pred), y = super().__getitem__(idx)
+        lo, hi = self._rows(idx)
+        users = self._user_rows(lo, hi)
+        if self.eval_mode:
+            users = np.repeat(users, np.diff(self._inv_off[lo: hi + 1]))
+        return (users.reshape(-1, 1), his, pred), y
+
+    def index_batch(self, idx):
+        """Train batch as user indexes + article-row numbers: ((user (B,), his (B,H), pred (B,C)), y (B,C))."""
+        (his, pred), y = super().index_batch(idx)
+        lo, hi = self._rows(idx)
+        return (self._user_rows(lo, hi), his, pred), y
+
+    def compact_eval_batch(self, idx):
+        """Eval batch without the per-candidate repetition: (user (b,), his (b,H,T), pred (sum C_i, T), impression_of_row
+        (sum C_i,), y (sum C_i, 1))."""
+        lo, hi = self._rows(idx)
+        return (self._user_rows(lo, hi),) + tuple(super().compact_eval_batch(idx))

@@ -1,10 +1,10 @@
-"""Hyper-parameter holders for the MI355X NRMS / NRMSDocVec path.
+"""Hyper-parameter holders for the MI355X NRMS / NRMSDocVec / NPA path.
 
 Same contract as the reference's ``model_config.py:82-114``: plain classes whose CLASS
 attributes are read by the model (``hparams.title_size`` ...) and may be overwritten in place
 by driver scripts (``ebnerd_nrms.py:85-96``); any attribute-bearing object works.  Only the
-two model families on the hot path are provided (NPA / LSTUR / NAML are out of scope,
-SURVEY.md section 2 rows 6).
+model families on the hot path are provided (LSTUR / NAML are out of scope, SURVEY.md section 2
+rows 6).
 """
 from __future__ import annotations
 
@@ -57,3 +57,22 @@ class hparams_nrms_docvec(_OptimizerDefaults):
     attention_hidden_dim = 200
     newsencoder_units_per_layer = [512, 512, 512]
     newsencoder_l2_regularization = 1e-4
+
+
+class hparams_npa(_OptimizerDefaults):
+    """reference model_config.py:64-79."""
+    __annotations__ = {
+        "title_size": int, "history_size": int, "n_users": int, "cnn_activation": str, "attention_hidden_dim": int,
+        "user_emb_dim": int, "filter_num": int, "window_size": int, "optimizer": str, "loss": str, "dropout": float,
+        "learning_rate": float,
+    }
+    # input dimensions
+    title_size = DEFAULT_TITLE_SIZE
+    history_size = 20
+    n_users = 50000
+    # architecture
+    cnn_activation = "relu"
+    attention_hidden_dim = 200
+    user_emb_dim = 400
+    filter_num = 400
+    window_size = 3

@@ -618,6 +618,63 @@ typedef struct ebn_dvn_finale {
 int ebn_dvn_finale_f32(const ebn_dvn_args* args, const ebn_tn_problem* problems, int32_t n, const ebn_dvn_finale* fin,
                        const ebn_step_state* st, ebn_stream_t stream);
 
+/* ---- NPA (npa.py:120-136 news encoder, layers.py:312-339 PersonalizedAttentivePooling) -------------------------------------
+ * Dropout sites of an NPA training step (keys in ebn_step_state.drop_key): Dropout(p) after the Conv1D (npa.py:129), the 0.2
+ * Dropout at the input of the news-level pooling (layers.py:324) and of the user-level pooling. */
+#define EBN_SITE_NPA_CONV 2
+#define EBN_SITE_NPA_NEWS_PAP 3
+#define EBN_SITE_NPA_USER_PAP 4
+
+/* Conv1D(F, window, activation="relu", padding="same") + Dropout(p) + the pooling's Dropout(0.2) (npa.py:120-129, layers.py:324)
+ * as an implicit GEMM on the exact-fp32 MFMA: X [n_titles*T, E] are the gathered (dropped-out) tokens, titles of T rows
+ * contiguous; W [window*E, F] is the Keras kernel (window, E, F) flattened, bias [F].  "same" padding: (window-1)/2 rows on
+ * the left, the rest on the right, taps outside a title read zero (no im2col image, no padded copy of X).
+ *   Vd[r, f] = relu(sum_{j,e} X[r + j - (window-1)/2, e] W[j*E + e, f] + bias[f]) * drop(conv_site, conv_p) * drop(pap_site, pap_p)
+ * with the dropout stream of ebn_gather_rows_f32 at element index r*F + f (st == NULL or p == 0: no dropout).  Vd is the only
+ * activation the backward needs.  E % 4 == 0, F % 4 == 0, window <= 15, X / W 16-byte aligned (EBN_ERR_UNSUPPORTED /
+ * EBN_ERR_ALIGN otherwise).                                                                                                    */
+int ebn_conv1d_fwd_f32(const float* X, const float* W, const float* bias, float* Vd, int64_t n_titles, int32_t T, int32_t E,
+                       int32_t F, int32_t window, const ebn_step_state* st, int32_t conv_site, float conv_p, int32_t pap_site,
+                       float pap_p, ebn_stream_t stream);
+/* Backward-data of the same: dX [n_titles*T, E] (overwritten) = the transposed convolution (taps reversed) of
+ * dY' = d(pre-activation), which is derived on the fly from the forward's Vd and its gradient dVd [n_titles*T, F]:
+ * dY' = dVd / ((1 - conv_p)(1 - pap_p)) where Vd > 0 and 0 elsewhere (Vd > 0 iff the ReLU passed and both masks kept).
+ * conv_p / pap_p as given to the forward (st == NULL: no dropout was applied).  Same shape rules; dVd / Vd / W aligned.      */
+int ebn_conv1d_bwd_data_f32(const float* dVd, const float* Vd, const float* W, float* dX, int64_t n_titles, int32_t T, int32_t E,
+                            int32_t F, int32_t window, const ebn_step_state* st, float conv_p, float pap_p, ebn_stream_t stream);
+/* Backward-weight: partials [splits][window*E + 1][F] = deterministic split-K slices (over the token rows) of
+ * [dW ; db] = [A(X)^T ; 1^T] . dY' -- rows 0 .. window*E-1 the kernel gradient, row window*E the bias gradient.  Their sum is
+ * left to ebn_grad_finish_f32 (EBN_FINISH_SPLITK job: n_parts = splits, rows = window*E + 1, cols = F), i.e. the gradient is
+ * the same bits for the same `splits` on every run.  ebn_conv1d_wgrad_splits: the split count the library suggests for the
+ * shape (1..64); ebn_conv1d_wgrad_workspace_floats: the size of `partials` for a split count (0 for an invalid problem).     */
+int ebn_conv1d_wgrad_splits(int64_t n_titles, int32_t T, int32_t E, int32_t F, int32_t window);
+int64_t ebn_conv1d_wgrad_workspace_floats(int64_t n_titles, int32_t T, int32_t E, int32_t F, int32_t window, int32_t splits);
+int ebn_conv1d_bwd_weight_f32(const float* X, const float* dVd, const float* Vd, float* partials, int32_t splits, int64_t n_titles,
+                              int32_t T, int32_t E, int32_t F, int32_t window, const ebn_step_state* st, float conv_p, float pap_p,
+                              ebn_stream_t stream);
+
+/* PersonalizedAttentivePooling after its Dense(A) matmul (layers.py:324-336), one workgroup per sequence n of L rows:
+ *   U <- tanh(U + ba) in place ([n_seq*L, A], U = Vd.Wa from ebn_gemm_f32);  s_l = Q[q_idx[n]] . U_l  (Q [n_q, A]: the query
+ *   Dense of each impression, npa.py:134 / :99; q_idx a DEVICE int32 [n_seq], rows outside [0, n_q) read row 0);
+ *   w = softmax_l(s) (max-subtracted, no +1e-7);  out[n] = sum_l w_l V_l  (V [n_seq*L, F], out [n_seq, F], w [n_seq*L]).
+ * out_d (may be NULL): out_d[n] = Dropout(drop_p, site)(out[n]) for n < n_drop (element index n*F + f) -- the 0.2 input
+ * dropout of the NEXT pooling (the user encoder's, layers.py:324), written in the same pass.  L <= 256, F <= 4096.        */
+int ebn_pap_fwd_f32(float* U, const float* ba, const float* Q, const int32_t* q_idx, int64_t n_q, const float* V, float* out,
+                    float* w, float* out_d, int64_t n_drop, int64_t n_seq, int32_t L, int32_t F, int32_t A,
+                    const ebn_step_state* st, int32_t site, float drop_p, ebn_stream_t stream);
+/* Its backward.  dout [n_seq, F]: rows n < n_drop are first multiplied IN PLACE by the dropout multiplier of (site, drop_p)
+ * (the backward of out_d); then dw_l = dout . V_l, ds = w (dw - sum w dw), dq [n_seq, A] = sum_l ds_l U_l (one row per
+ * SEQUENCE: ebn_pap_dq_reduce_f32 sums them per query row), U <- d(pre-tanh) = ds q (1 - U^2) in place, and, when dV is not
+ * NULL, dV [n_seq*L, F] = w (x) dout (the pooling's direct term; the term through Wa is dpre.Wa^T -- callers that fold both
+ * into one pass pass NULL and use ebn_gemm_f32_rank1).                                                                    */
+int ebn_pap_bwd_f32(float* U, const float* Q, const int32_t* q_idx, int64_t n_q, const float* V, const float* w, float* dout,
+                    float* dV, float* dq, int64_t n_drop, int64_t n_seq, int32_t L, int32_t F, int32_t A,
+                    const ebn_step_state* st, int32_t site, float drop_p, ebn_stream_t stream);
+/* dQ[i] = sum of dq[n] over the sequences n with q_idx[n] == i, in ascending n (fixed order, no atomics): the per-impression
+ * gradient of the query when every impression's H + C titles share its query (npa.py:99-103,185-190).                      */
+int ebn_pap_dq_reduce_f32(const float* dq, const int32_t* q_idx, int64_t n_seq, float* dQ, int64_t n_q, int32_t A,
+                          ebn_stream_t stream);
+
 /* Step prologue: copy up to three device buffers (history ids, candidate ids, labels of a batch handed over as device
  * tensors -- the inputs of nrms.py:170-176) into the step's static buffers with ONE launch; n_i in bytes, multiples
  * of 4; a NULL source or n_i = 0 skips that pair.                                                                   */
