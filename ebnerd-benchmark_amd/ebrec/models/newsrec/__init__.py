@@ -1,5 +1,5 @@
-"""MI355X-native NRMS / NRMSDocVec / NPA (LSTUR and NAML of the reference are out of scope)."""
-from .model_config import hparams_npa, hparams_nrms, hparams_nrms_docvec, hparams_to_dict, print_hparams  # noqa: F401
+"""MI355X-native NRMS / NRMSDocVec / NPA / LSTUR (NAML of the reference is out of scope)."""
+from .model_config import hparams_lstur, hparams_npa, hparams_nrms, hparams_nrms_docvec, hparams_to_dict, print_hparams  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing model_config / dataloader must not need torch or a GPU
@@ -12,4 +12,7 @@ def __getattr__(name):  # lazy: importing model_config / dataloader must not nee
     if name == "NPAModel":
         from .npa import NPAModel
         return NPAModel
+    if name == "LSTURModel":
+        from .lstur import LSTURModel
+        return LSTURModel
     raise AttributeError(name)

@@ -1,0 +1,87 @@
+"""LSTURModel on MI355X: the reference's constructor-and-attribute surface (lstur.py:12-201) over hand-written HIP kernels.
+
+    model = LSTURModel(hparams=hparams_lstur, word2vec_embedding=emb, seed=42)
+    model.model.fit(train_loader, validation_data=val_loader, epochs=5)      # LSTURDataLoader batches
+    scores = model.scorer.predict(test_loader)
+
+Inputs are ``(user_indexes (B,1), his_input_title (B,H,T), pred_input_title (B,C,T))`` as in the reference
+(lstur.py:195 ``keras.Model([user_indexes, his_input_title, pred_input_title], preds)``).  Deliberate differences:
+  * one GPU, through libebnerd_hip.so only (RuntimeError otherwise -- no CPU fallback, no multi-rank form);
+  * dropout uses the build's counter-based stream, not TF's (statistical parity only);
+  * weights are saved as a named torch file (``model.model.save_weights``); TF weight lists are not imported.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ._engine import glorot_uniform_np
+from ._engine_lstur import LSTUREngine
+from ._keras_like import ScorerModel, TrainModel
+
+
+class LSTURModel:
+    """LSTUR (An et al., ACL 2019): CNN title encoder with masked additive attention, and a GRU over the clicked titles
+    combined with a trainable long-term user-id embedding -- as the GRU's initial state (type "ini") or concatenated with its
+    output (type "con") (reference lstur.py)."""
+
+    def __init__(self, hparams, word2vec_embedding: np.ndarray = None, word_emb_dim: int = 300, vocab_size: int = 32000,
+                 seed: int = None, *, train_embedding: bool = True, device=None, process_group=None, bce_on: str = "logits"):
+        self.hparams = hparams
+        self.seed = seed
+        if seed is not None:
+            np.random.seed(seed)
+            torch.manual_seed(seed)
+        if word2vec_embedding is None:
+            self.word2vec_embedding = glorot_uniform_np((vocab_size, word_emb_dim), seed)
+        else:
+            self.word2vec_embedding = word2vec_embedding
+        self._get_loss(hparams.loss)
+        self._get_opt(hparams.optimizer, hparams.learning_rate)
+        if getattr(hparams, "cnn_activation", "relu") != "relu":
+            raise ValueError(f"cnn_activation {hparams.cnn_activation!r}: the HIP Conv1D implements relu")
+        self._engine = LSTUREngine(
+            np.asarray(self.word2vec_embedding), hparams.n_users, hparams.title_size, hparams.history_size, hparams.filter_num,
+            hparams.window_size, hparams.attention_hidden_dim, hparams.gru_unit, getattr(hparams, "type", "ini"), hparams.dropout,
+            hparams.learning_rate, hparams.loss, seed=seed, train_embedding=train_embedding, device=device,
+            process_group=process_group, bce_on=bce_on)
+        self.model, self.scorer = self._build_graph()
+
+    def _get_loss(self, loss: str):
+        if loss == "cross_entropy_loss":
+            return "categorical_crossentropy"
+        if loss == "log_loss":
+            return "binary_crossentropy"
+        raise ValueError(f"this loss not defined {loss}")
+
+    def _get_opt(self, optimizer: str, lr: float):
+        if optimizer == "adam":
+            return "adam"
+        raise ValueError(f"this optimizer not defined {optimizer}")
+
+    def _set_loss(self, loss: str):
+        self._get_loss(loss)
+        self._engine.loss = loss
+
+    def _build_graph(self):
+        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
+
+    # -- scorer bodies (lstur.py:191-200: sigmoid(news(pred_one) . user)) ------------------------------------------------------
+    def _score_pairs(self, user, his, pred_one) -> torch.Tensor:
+        """sigmoid(cand_i . user_i) for every row i of (user (N,1), his (N,H,T), pred_one (N,1,T))."""
+        his = np.asarray(his)
+        n = his.shape[0]
+        cands = np.asarray(pred_one).reshape(-1, self._engine.T)
+        if cands.shape[0] != n:
+            raise ValueError(f"scorer expects one candidate per history row, got {his.shape} vs {np.shape(pred_one)}")
+        return self._engine.pair_scores(np.asarray(user).reshape(-1), his, cands, np.arange(n), sigmoid=True)
+
+    def _score_compact(self, user, his, cands, rows) -> torch.Tensor:
+        """The same scores for the loader's compact eval layout: user (b,), his (b,H,T) once per impression, cands (n,T),
+        rows[i] = impression of candidate i.  Candidates are encoded per batch (no article cache)."""
+        return self._engine.pair_scores(np.asarray(user).reshape(-1), np.asarray(his), np.asarray(cands), np.asarray(rows),
+                                        sigmoid=True)
+
+    def train_step(self, user, his, pred, y):
+        """One optimizer step on raw arrays; returns the batch loss (device tensor)."""
+        return self._engine.train_step(user, his, pred, y)

@@ -1,10 +1,9 @@
-"""Hyper-parameter holders for the MI355X NRMS / NRMSDocVec / NPA path.
+"""Hyper-parameter holders for the MI355X NRMS / NRMSDocVec / NPA / LSTUR path.
 
 Same contract as the reference's ``model_config.py:82-114``: plain classes whose CLASS
 attributes are read by the model (``hparams.title_size`` ...) and may be overwritten in place
 by driver scripts (``ebnerd_nrms.py:85-96``); any attribute-bearing object works.  Only the
-model families on the hot path are provided (LSTUR / NAML are out of scope, SURVEY.md section 2
-rows 6).
+model families on the hot path are provided (NAML is out of scope).
 """
 from __future__ import annotations
 
@@ -74,5 +73,25 @@ class hparams_npa(_OptimizerDefaults):
     cnn_activation = "relu"
     attention_hidden_dim = 200
     user_emb_dim = 400
+    filter_num = 400
+    window_size = 3
+
+
+class hparams_lstur(_OptimizerDefaults):
+    """reference model_config.py:45-61."""
+    __annotations__ = {
+        "title_size": int, "history_size": int, "n_users": int, "cnn_activation": str, "type": str,
+        "attention_hidden_dim": int, "gru_unit": int, "filter_num": int, "window_size": int, "optimizer": str, "loss": str,
+        "dropout": float, "learning_rate": float,
+    }
+    # input dimensions
+    title_size = DEFAULT_TITLE_SIZE
+    history_size = 20
+    n_users = 50000
+    # architecture
+    cnn_activation = "relu"
+    type = "ini"
+    attention_hidden_dim = 200
+    gru_unit = 400
     filter_num = 400
     window_size = 3

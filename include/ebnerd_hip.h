@@ -675,6 +675,36 @@ int ebn_pap_bwd_f32(float* U, const float* Q, const int32_t* q_idx, int64_t n_q,
 int ebn_pap_dq_reduce_f32(const float* dq, const int32_t* q_idx, int64_t n_seq, float* dQ, int64_t n_q, int32_t A,
                           ebn_stream_t stream);
 
+/* ---- LSTUR (lstur.py:56-144 user and news encoders, layers.py:55-81 AttLayer2, layers.py:273-309 Compute/OverwriteMasking) ---
+ * The news encoder reuses ebn_conv1d_* (Dropout(p) at site EBN_SITE_NPA_CONV, the pooling dropout passed as p = 0) and the
+ * AttLayer2 backward (ebn_attpool_bwd_pool_f32 / ebn_attpool_bwd_dpre_f32, linear in w: masked rows get zero gradients).
+ *
+ * AttLayer2 under the title encoder's mask (lstur.py:136-141): ebn_attpool_fwd_f32 with the token ids [n_seq*L] of the rows:
+ *   U <- tanh(U + b) in place;  m_l = (ids_l != 0) && any(X_l != 0)  (OverwriteMasking by token != 0, then Masking());
+ *   a_l = m_l exp(U_l . q) (no max-subtraction);  w_l = a_l / (sum a + 1e-7);  out = sum_l w_l X_l.
+ * A masked row gets w_l == 0 exactly; a title of padding only gets out == 0.  X is the conv output Vd (not zeroed at
+ * padding: the mask covers those rows).                                                                                       */
+int ebn_attpool_masked_fwd_f32(float* U, const float* b, const float* q, const float* X, const int32_t* ids, float* out,
+                               float* w, int64_t n_seq, int32_t L, int32_t E, int32_t A, ebn_stream_t stream);
+/* Masked Keras GRU recurrence (lstur.py:81-104; TF2 GRU defaults: reset_after=True, sigmoid / tanh), B sequences of H steps,
+ * enqueued as one launch per step on `stream` (no allocation, no sync: capturable).
+ *   gx [B*H, 3U] = X . kernel (one ebn_gemm_f32 beforehand; row b*H + t), X [B*H, F] the history news vectors, Wrec [U, 3U] the
+ *   recurrent kernel, bias [2, 3U] (row 0 input, row 1 recurrent); column blocks [z | r | h] throughout.
+ *   z = sig(gx_z + b_z + h.Wrec_z + b'_z), r = sig(... r ...), n = tanh(gx_h + b_h + r (h.Wrec_h + b'_h)), h' = z h + (1-z) n;
+ *   step t of sequence b is masked (Masking(0.0): h' = h) iff X[b*H + t] is all zero -- derived in the kernel.
+ * h0 [B, U] or NULL (zeros).  Out: Hs [H+1, B, U] time-major with Hs[0] = h0 (Hs[H] is the output), act [H, B, 4U] =
+ * z | r | n | (h.Wrec_h + b'_h) per step (zeros on masked steps).  F % 4 == 0, U % 4 == 0, H <= 4096, X / Wrec / h0 / Hs
+ * 16-byte aligned.                                                                                                            */
+int ebn_gru_fwd_f32(const float* gx, const float* X, const float* Wrec, const float* bias, const float* h0, float* Hs,
+                    float* act, int64_t B, int32_t H, int32_t F, int32_t U, ebn_stream_t stream);
+/* Its backward in reverse time (H + 1 launches): dhH [B, U] = dL/dHs[H] (not modified).  Out: dgx [B*H, 3U] = dL/d(gx + b)
+ * (row b*H + t), dgh [H, B, 3U] = dL/d(h.Wrec + b') -- both zero rows on masked steps -- and dh0 [B, U] = dL/dh0 (a masked
+ * step passes dh through unchanged).  The weight gradients follow on the GEMMs: dWrec = Hs[0:H]^T . dgh (K = H*B),
+ * dkernel = X^T . dgx, dX = dgx . kernel^T, the bias rows are the column sums of dgx and dgh.  Same shape rules; dh0 must not
+ * alias dhH; X / Wrec / dgh 16-byte aligned.                                                                                  */
+int ebn_gru_bwd_f32(const float* dhH, const float* X, const float* Wrec, const float* Hs, const float* act, float* dgx,
+                    float* dgh, float* dh0, int64_t B, int32_t H, int32_t F, int32_t U, ebn_stream_t stream);
+
 /* Step prologue: copy up to three device buffers (history ids, candidate ids, labels of a batch handed over as device
  * tensors -- the inputs of nrms.py:170-176) into the step's static buffers with ONE launch; n_i in bytes, multiples
  * of 4; a NULL source or n_i = 0 skips that pair.                                                                   */
