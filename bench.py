@@ -1,10 +1,15 @@
 #!/usr/bin/env python
 """Headline benchmark of the MI355X-native NRMS training path.
 
-    python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4|c5|c5h50] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4|c5|c5h50] [--dump-outputs DIR] [--full]
 
 K is the number of timed steps in all (dealt over --repeats windows; `ms_per_step` is the median window's).  With
 --dump-outputs, what the final timed step computed is written as DIR/<name>.npy (see dump_outputs()).
+
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, the dump if asked, and the
+JSON line.  Everything else the benchmark measures -- the kernel rooflines and their rocprofv3 passes, the HBM calibration,
+the counted launches per step, the split-precision and model.fit legs, the CPU baseline, the other configs as `legs`, and
+at N > 1 the re-timing without collectives behind `comm_exposed_us` -- runs only with --full.
 
 N > 1: either launched by ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`` (one rank per
 GPU over RCCL), or started directly, in which case it re-launches itself that way.  With fewer visible GPUs than ranks
@@ -19,12 +24,13 @@ lookup, batch 32 per GPU.  Multi-GPU = data parallel, weak scaling (per-GPU batc
 data-path collective other than the gradient all-reduce.  Inputs are resident in HBM before the
 timed region starts.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (all but roofline_step with --full only):
   roofline        the time-dominant kernel (the Q|K|V projection GEMM, MFMA-bound) on the step's own buffers and
                   arguments: 10 launches captured into a hipGraph (the launch path of the timed region), HIP events
                   on the launch stream around 5 replays
   roofline_gather the title-embedding gather (HBM-bound) the metric string names, same method
   roofline_step   the WHOLE step against the exact-fp32 MFMA peak: exact matmul FLOPs of one step / the step's time
+                  (its counted `launches_per_step` with --full only: counting takes a step of its own)
   cpu_baseline    oracle/nrms_torch.py (fp32 torch-eager port of the reference math; the reference's
                   TF path cannot run here) timed on the host cores: 20 timed steps after 5 warm-ups
 
@@ -607,14 +613,17 @@ def bench_docvec(args, c, world, rank, device, sync, dfields, multi=False):
     times, last = timed_repeats(lambda k, last: eng.train_step(*batches[k % 8], indexed=True, return_probs=last), args, sync, world, device)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, eng, last)
-    n_launches = launches_of_one_step(eng, lambda: eng.train_step(*batches[0], indexed=True), sync)
+    loss = float(eng.loss_dev.item())  # the final timed step's (before --full's extra step and kernel launches)
+    n_launches = launches_of_one_step(eng, lambda: eng.train_step(*batches[0], indexed=True), sync) if args.full else None
     # kernel-level rooflines on the step's own buffers: the document-vector gather (HBM) and the time-dominant launch of the step,
     # the grouped weight-gradient product of all Dense kernels (MFMA)
     rk = eng.roofline_kernels(c["B"], c["C"])
-    id_sets = [torch.cat([h.reshape(-1), p.reshape(-1)]).contiguous() for h, p, _ in batches]  # the 8 batches' row numbers
-    kt = {"gather": time_kernel([rk["gather"](ids) for ids in id_sets], sync)}
-    if "dw_group" in rk:
-        kt["dw_group"] = time_kernel(rk["dw_group"], sync)
+    kt = {}
+    if not args.no_roofline:
+        id_sets = [torch.cat([h.reshape(-1), p.reshape(-1)]).contiguous() for h, p, _ in batches]  # the 8 batches' row numbers
+        kt["gather"] = time_kernel([rk["gather"](ids) for ids in id_sets], sync)
+        if "dw_group" in rk:
+            kt["dw_group"] = time_kernel(rk["dw_group"], sync)
     if rank == 0:
         n_rows = c["B"] * (c["H"] + c["C"])
         E, A, H, B, C = c["h"] * c["d"], c["A"], c["H"], c["B"], c["C"]
@@ -631,7 +640,7 @@ def bench_docvec(args, c, world, rank, device, sync, dfields, multi=False):
                 "config": {"workload": f"NRMSDocVec train step, BASELINE.json configs[2] (c3): {c['n_articles']} x {c['doc']} document vectors in HBM, "
                                        f"MLP {c['units']} -> {c['h'] * c['d']}, history_size={c['H']} npratio={c['C'] - 1}, dropout 0.2, adam lr=1e-4",
                            "global_batch": world * c["B"], "per_gpu_batch": c["B"], "parallelism": f"dp{world}",
-                           "final_loss": float(eng.loss_dev.item())}, **dfields, "oracle_pin": oracle_pin_status(), "env": nondefault_env()}
+                           "final_loss": loss}, **dfields, "oracle_pin": oracle_pin_status(), "env": nondefault_env()}
         gather_bytes = n_rows * (4 + 2 * c["doc"] * 4)
         src = "measured in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over `bench.py --config c3 --kernel-probe`, (2 x FETCH_SIZE + WRITE_SIZE) KiB per launch" \
             if probe else "not measured (no rocprofv3 passes in this run)"
@@ -646,19 +655,21 @@ def bench_docvec(args, c, world, rank, device, sync, dfields, multi=False):
                                 "frac": fl / kt["dw_group"] / 1e12 / MFMA_F32_PEAK_TFLOPS, "traffic": (probe or {}).get("dw_group", {}).get("traffic"),
                                 "traffic_source": src, "avg_launch_us": kt["dw_group"] * 1e6, "algorithmic_flops_per_launch": fl,
                                 "algorithmic_bytes_per_launch": rk["dw_group_bytes"]}
-        line["roofline_gather"] = {"kernel": (probe or {}).get("gather", {}).get("name", "gather_rows_vec4_kernel") + " (document-vector gather)", "bound": "hbm",
-                                   "achieved": gather_bytes / kt["gather"] / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                   "frac": gather_bytes / kt["gather"] / 1e9 / HBM_PEAK_GBS, "traffic": (probe or {}).get("gather", {}).get("traffic"),
-                                   "traffic_source": src, "avg_launch_us": kt["gather"] * 1e6, "algorithmic_bytes_per_launch": gather_bytes}
+        if "gather" in kt:
+            line["roofline_gather"] = {"kernel": (probe or {}).get("gather", {}).get("name", "gather_rows_vec4_kernel") + " (document-vector gather)", "bound": "hbm",
+                                       "achieved": gather_bytes / kt["gather"] / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                       "frac": gather_bytes / kt["gather"] / 1e9 / HBM_PEAK_GBS, "traffic": (probe or {}).get("gather", {}).get("traffic"),
+                                       "traffic_source": src, "avg_launch_us": kt["gather"] * 1e6, "algorithmic_bytes_per_launch": gather_bytes}
         ms = line["ms_per_step"]
         line["roofline_step"] = {"what": "the whole training step against the exact-fp32 MFMA peak: exact matmul FLOPs of one step (every Dense product of the "
                                          "news encoder forward / weight gradient / input gradient, the user encoder, the scorer) / ms_per_step",
                                  "bound": "mfma", "achieved": fl_step / (ms * 1e-3) / 1e12, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                 "frac": fl_step / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, "flops_per_step": fl_step,
-                                 "launches_per_step": n_launches,
-                                 "launches_note": "counted (ebn_launch_count around one eager step of this engine; the hipGraphs replay the same launches): "
-                                                  f"news-encoder MLP of {len(c['units'])} hidden layers in the {'fused' if 'dw_group' in rk else 'per-pass'} form, "
-                                                  "the user stage, Adam"}
+                                 "frac": fl_step / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, "flops_per_step": fl_step}
+        if n_launches is not None:
+            line["roofline_step"].update({"launches_per_step": n_launches,
+                                          "launches_note": "counted (ebn_launch_count around one eager step of this engine; the hipGraphs replay the same launches): "
+                                                           f"news-encoder MLP of {len(c['units'])} hidden layers in the {'fused' if 'dw_group' in rk else 'per-pass'} form, "
+                                                           "the user stage, Adam"})
         if not multi and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_docvec(c)
         print("\n" + json.dumps(line), flush=True)  # (own line even when a library -- gloo -- has left an unterminated one on stdout)
@@ -797,7 +808,7 @@ def run_legs(args, world, rank, device, watchdog):
         env.update(MASTER_ADDR=os.environ.get("MASTER_ADDR", "127.0.0.1"), MASTER_PORT=str(port[0]), EBN_BENCH_LEG="1")
         cmd = [sys.executable, str(Path(__file__).resolve()), "--leg", "--config", cfg, "--gpus", str(world), "--steps", str(args.steps),
                "--warmup", str(args.warmup), "--repeats", str(args.repeats), "--ids", args.ids, "--graph-collectives", args.graph_collectives,
-               "--no-roofline", "--no-probe", "--no-cpu-baseline"] + (["--no-graph"] if args.no_graph else []) + (["--force-dist"] if args.force_dist else [])
+               "--full", "--no-roofline", "--no-probe", "--no-cpu-baseline"] + (["--no-graph"] if args.no_graph else []) + (["--force-dist"] if args.force_dist else [])
         watchdog.arm(f"leg {cfg}: child processes (own timeout {leg_timeout:.0f} s)")
         watchdog._deadline = time.monotonic() + leg_timeout + 60.0  # the child's own timeout fires first
         t0 = time.perf_counter()
@@ -850,7 +861,7 @@ def run_legs_single_gpu(args):
             out[cfg] = {"skipped": "this process runs under a profiler: profile the leg directly with --config " + cfg}
             continue
         cmd = [sys.executable, str(Path(__file__).resolve()), "--leg", "--config", cfg, "--gpus", "1", "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--repeats", str(args.repeats), "--ids", args.ids, "--no-fit-loop", "--no-split-leg"] + \
+               "--warmup", str(args.warmup), "--repeats", str(args.repeats), "--ids", args.ids, "--full", "--no-fit-loop", "--no-split-leg"] + \
               (["--no-graph"] if args.no_graph else []) + (["--no-probe"] if args.no_probe else []) + (["--no-roofline"] if args.no_roofline else []) + \
               ([] if (cfg == "c3" and not args.no_cpu_baseline) else ["--no-cpu-baseline"])
         t0 = time.perf_counter()
@@ -913,6 +924,11 @@ def main():
     ap.add_argument("--ids", default="uniform", choices=["uniform", "zipf"],
                     help="SURVEY.md 8(d) id distribution: uniform (U, the headline) or zipf (Z: Zipf(1.0) ids + 15 %% of the history slots "
                          "all-zero titles -- hot row 0, as real left-padded EB-NeRD batches have)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: kernel rooflines (with their rocprofv3 passes) and the HBM calibration, "
+                         "the counted launches per step, the split-precision and model.fit legs, the CPU baseline, the other configs as --legs, "
+                         "and at N > 1 the re-timing without collectives (comm_exposed_us).  --no-cpu-baseline, --no-fit-loop, --no-split-leg, "
+                         "--no-roofline, --no-probe and --legs trim a --full run; without --full none of it runs but configs that --legs names")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch kernel by kernel instead of hipGraph replay")
     ap.add_argument("--graph-collectives", nargs="?", const="on", default="off", choices=["off", "on", "auto"],
@@ -934,8 +950,8 @@ def main():
                     help="trainable table: one 64-bit atomic per gradient element instead of combining the duplicate ids of every 64 consecutive "
                          "tokens first (same bits; the A/B behind the default (profiles/HISTORY.md), see --ids zipf)")
     ap.add_argument("--legs", default=None, help="on the default config: also measure these configs as sub-records of the line, each in its own (set of) child "
-                                                  "process(es) under its own timeout ('' = none).  Default: N = 1 -> c1,c3,c4,c5 (every other BASELINE.json config at "
-                                                  "its single-GPU / per-rank shape, with its own roofline objects); N > 1 -> c4,c5 (configs[3] / configs[4])")
+                                                  "process(es) under its own timeout ('' = none).  Default: none; with --full, N = 1 -> c1,c3,c4,c5 (every other "
+                                                  "BASELINE.json config at its single-GPU / per-rank shape, with its own roofline objects); N > 1 -> c4,c5 (configs[3] / configs[4])")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the MULTI-RANK branch on a group of one rank: through torch.distributed.run, init_process_group('nccl', device_id=...), "
                          "rccl_view, SegmentTrace, HangWatchdog, the engine's multi-rank launch form (collectives between the graph replays -- identities "
@@ -956,6 +972,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
         ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing else
+        args.no_cpu_baseline = args.no_fit_loop = args.no_split_leg = args.no_roofline = args.no_probe = True
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -969,7 +987,7 @@ def main():
     backend = None
     multi = world > 1 or args.force_dist  # the multi-rank branch (a one-rank group under --force-dist)
     if args.legs is None:
-        args.legs = "c4,c5" if multi else "c1,c3,c4,c5"
+        args.legs = ("c4,c5" if multi else "c1,c3,c4,c5") if args.full else ""
     if multi:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         # "nccl" = RCCL over xGMI; RCCL refuses two ranks on one GPU, so a box with fewer GPUs than ranks falls back to gloo
@@ -1060,7 +1078,8 @@ def main():
     times, last = timed_repeats(lambda k, last: eng.train_step(*batches[k % len(batches)], return_probs=last), args, sync, world, device)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, eng, last)
-    n_launches = launches_of_one_step(eng, lambda: eng.train_step(*batches[0]), sync) if not multi else None
+    loss = float(eng.loss_dev.item())  # the final timed step's (before --full's extra step and kernel launches)
+    n_launches = launches_of_one_step(eng, lambda: eng.train_step(*batches[0]), sync) if args.full and not multi else None
     # Kernel-level rooflines: the Q|K|V projection GEMM and the embedding gather of THIS step (same buffers, same
     # arguments), each captured into a hipGraph of 10 launches and timed with HIP events on the launch stream.
     rk = eng.roofline_kernels(c["B"], c["C"])
@@ -1069,9 +1088,8 @@ def main():
     if not args.no_roofline:
         kt = {"qkv_gemm": time_kernel(rk["qkv_gemm"], sync), "gather": time_kernel([rk["gather"](ids) for ids in id_sets], sync)}
         calib = hbm_calibration(sync, device)
-    loss = float(eng.loss_dev.item())
     comm = None
-    if multi:
+    if multi and args.full:
         phase(f"{args.config}: the same steps re-timed without collectives (comm_exposed_us)")
         # what the collectives cost the step: the same steps timed again with every collective skipped (the results of those
         # steps are wrong and thrown away; all ranks skip together) -- exposed = with - without, after whatever the overlap hid
@@ -1210,6 +1228,7 @@ def main():
             line["exchange"] = eng.exchange.stats()
         if multi:
             line["allreduce_bytes_per_step"] = eng.allreduce_bytes(c["B"] * (c["H"] + c["C"]) * c["T"])
+        if comm is not None:
             line["comm_exposed_us"] = (line["ms_per_step"] - comm["ms_per_step_without_collectives"]) * 1e3
             line["comm"] = {**comm, "note": "comm_exposed_us = ms_per_step - the same steps with every collective skipped (measured after the timed region, same graphs).  "
                                             "The dense gradients travel as one flat bucket: with a trainable table it is started asynchronously after the dWqkv GEMM and "

@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the driver's fields, the roofline of the dominant kernel and (at N = 1) the CPU baseline."""
+"""bench.py prints ONE JSON line with the driver's fields; with --full also the roofline of the dominant kernel and (at N = 1) the CPU baseline."""
 import json
 import subprocess
 import sys
@@ -12,7 +12,7 @@ ROOT = Path(__file__).resolve().parents[1]
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", ["c2", "c3"])
 def test_bench_line_carries_the_contract_fields(cfg):
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", cfg, "--steps", "3", "--warmup", "1", "--repeats", "2",
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--config", cfg, "--steps", "3", "--warmup", "1", "--repeats", "2",
                           "--cpu-steps", "3"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -90,6 +90,25 @@ def test_bench_line_carries_the_contract_fields(cfg):
         assert "cpu_baseline" not in legs["c1"] and legs["c5"]["config"]["global_batch"] == 64
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", ["c2", "c3"])
+def test_a_plain_run_prints_the_headline_and_nothing_that_takes_runs_of_its_own(cfg):
+    """Without --full: the warm-up, the timed steps and the line -- no kernel rooflines, calibration, counted launches, other
+    precisions, fit loop, CPU baseline or legs."""
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", cfg, "--steps", "3", "--warmup", "1", "--repeats", "2"],
+                         capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "training impressions/sec" and d["unit"] == "impressions/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and len(d["ms_per_step_repeats"]) == 2
+    assert d["value"] > 0 and abs(d["value"] - d["config"]["per_gpu_batch"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "roofline_gather", "cpu_baseline", "split_precision", "fit_loop", "legs"):
+        assert k not in d, k
+    assert "launches_per_step" not in d["roofline_step"] and d["roofline_step"]["achieved"] > 0
+
+
 def _bench(argv, timeout, env=None):
     import os
     import time
@@ -104,7 +123,7 @@ def _bench(argv, timeout, env=None):
 def test_multi_rank_line_carries_the_c4_and_c5_legs_and_the_communication_librarys_view():
     """Verdict r4 item 1: the driver's ONE command (`bench.py --gpus N`, no --config) must yield all the multi-GPU evidence.  Two ranks
     sharing this box's GPU over gloo (RCCL refuses two ranks on one device): a functional dry run of exactly that command."""
-    out, _ = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2"], 1500)
+    out, _ = _bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2"], 1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -136,7 +155,7 @@ def test_the_multi_rank_branch_runs_end_to_end_on_a_one_rank_rccl_group():
     plain, _ = _bench(["--steps", "20", "--warmup", "5", "--repeats", "3", "--legs", "", "--no-cpu-baseline", "--no-fit-loop", "--no-split-leg", "--no-probe"], 900)
     assert plain.returncode == 0, plain.stderr[-3000:]
     ref = json.loads([l for l in plain.stdout.splitlines() if l.startswith("{")][0])
-    out, _ = _bench(["--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "5", "--repeats", "3"], 1500)
+    out, _ = _bench(["--full", "--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "5", "--repeats", "3"], 1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

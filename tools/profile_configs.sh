@@ -8,7 +8,7 @@ tag=$1; shift
 mkdir -p gpurun_out/$tag
 for c in "$@"; do
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$tag/stats_$c -o $c -- \
-    python bench.py --config $c --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline \
+    python bench.py --full --config $c --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline \
     > gpurun_out/$tag/bench_${c}_under_rocprof.json 2> gpurun_out/$tag/rocprof_$c.err
   rm -f gpurun_out/$tag/stats_$c/*kernel_trace.csv gpurun_out/$tag/stats_$c/*agent_info.csv
 done
