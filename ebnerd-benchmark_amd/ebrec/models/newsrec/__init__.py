@@ -1,5 +1,5 @@
-"""MI355X-native NRMS / NRMSDocVec / NPA / LSTUR (NAML of the reference is out of scope)."""
-from .model_config import hparams_lstur, hparams_npa, hparams_nrms, hparams_nrms_docvec, hparams_to_dict, print_hparams  # noqa: F401
+"""MI355X-native NRMS / NRMSDocVec, NPA and LSTUR (user-id models), and NAML (multi-view news encoder)."""
+from .model_config import hparams_lstur, hparams_naml, hparams_npa, hparams_nrms, hparams_nrms_docvec, hparams_to_dict, print_hparams  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing model_config / dataloader must not need torch or a GPU
@@ -15,4 +15,7 @@ def __getattr__(name):  # lazy: importing model_config / dataloader must not nee
     if name == "LSTURModel":
         from .lstur import LSTURModel
         return LSTURModel
+    if name == "NAMLModel":
+        from .naml import NAMLModel
+        return NAMLModel
     raise AttributeError(name)

@@ -221,3 +221,100 @@ class LSTURDataLoader(NRMSDataLoader):
         (sum C_i,), y (sum C_i, 1))."""
         lo, hi = self._rows(idx)
         return (self._user_rows(lo, hi),) + tuple(super().compact_eval_batch(idx))
+
+
+@dataclass
+class NAMLDataLoader(NewsrecDataLoader):
+    """reference dataloader.py:266-419: the title, body, category and subcategory of every article of the history and of the
+    in-view list.  ``category_mapping`` / ``subcategory_mapping`` are keyed by ARTICLE id (as the reference applies them);
+    articles they do not name, and null ids, take ``unknown_category_value`` / ``unknown_subcategory_value``.  Bodies are looked
+    up in their own ``create_lookup_objects`` matrix of ``body_mapping`` (unknown articles: row 0).
+
+      train mode   ((his_title (B,H,T), his_body (B,H,Tb), his_vert (B,H,1), his_subvert (B,H,1),
+                     pred_title (B,C,T), pred_body (B,C,Tb), pred_vert (B,C,1), pred_subvert (B,C,1)), y (B,C))
+      eval mode    the same with every history repeated once per candidate and pred_* of shape (sum C_i, 1, .), y (sum C_i, 1)
+
+    Deliberate difference: the reference raises on ``eval_mode=True``; here eval mode is the layout its scorer takes (one
+    candidate per row), so that ``model.scorer.predict`` has a loader to run on.  ``compact_eval_batch`` hands the scorer the
+    histories once per impression instead.
+    """
+
+    unknown_category_value: int = 0
+    unknown_subcategory_value: int = 0
+    body_mapping: dict = None
+    category_mapping: dict = None
+    subcategory_mapping: dict = None
+
+    def __post_init__(self):
+        self.lookup_article_index_body, self.lookup_article_matrix_body = create_lookup_objects(
+            self.body_mapping, unknown_representation=self.unknown_representation)
+        super().__post_init__()
+        his_cells = self.X[self.history_column].tolist() if len(self.X) else []
+        inv_cells = self.X[self.inview_col].tolist() if len(self.X) else []
+        self._his_flat, self._his_off = _map_ids(his_cells, self.lookup_article_index)
+        self._inv_flat, self._inv_off = _map_ids(inv_cells, self.lookup_article_index)
+        self._hisb_flat, _ = _map_ids(his_cells, self.lookup_article_index_body)
+        self._invb_flat, _ = _map_ids(inv_cells, self.lookup_article_index_body)
+        self._his_cat = [self._categories(his_cells, m, u) for m, u in ((self.category_mapping, self.unknown_category_value),
+                                                                        (self.subcategory_mapping, self.unknown_subcategory_value))]
+        self._inv_cat = [self._categories(inv_cells, m, u) for m, u in ((self.category_mapping, self.unknown_category_value),
+                                                                        (self.subcategory_mapping, self.unknown_subcategory_value))]
+        self._y_flat = np.concatenate([np.asarray(l, dtype=np.int64) for l in self.y]) if len(self.y) else np.zeros(0, np.int64)
+        hl = np.diff(self._his_off)
+        if len(hl) and hl.min() != hl.max():
+            raise ValueError("history lists must all have the same length (truncate_history with a padding value)")
+        self._H = int(hl[0]) if len(hl) else 0
+
+    @staticmethod
+    def _categories(cells, mapping: dict, unknown: int) -> np.ndarray:
+        """article id -> category (int64) over the ragged cells; unknown / null ids -> `unknown`."""
+        shifted = {k: i + 1 for i, k in enumerate(mapping or {})}  # _map_ids sends unknown ids to 0: look up 1-based positions
+        values = np.concatenate([[int(unknown)], np.fromiter((int(v) for v in (mapping or {}).values()), dtype=np.int64,
+                                                             count=len(mapping or {}))])
+        pos, _ = _map_ids(cells, shifted)
+        return values[pos]
+
+    def _rows(self, idx):
+        lo = idx * self.batch_size
+        return lo, min(lo + self.batch_size, len(self.X))
+
+    def _history(self, lo, hi):
+        """(title rows, body rows, vert, subvert) of the histories of impressions lo..hi, each (hi-lo, H)."""
+        sl = slice(self._his_off[lo], self._his_off[hi])
+        shape = (hi - lo, self._H)
+        return (self._his_flat[sl].reshape(shape), self._hisb_flat[sl].reshape(shape), self._his_cat[0][sl].reshape(shape),
+                self._his_cat[1][sl].reshape(shape))
+
+    def _inview(self, lo, hi):
+        sl = slice(self._inv_off[lo], self._inv_off[hi])
+        return self._inv_flat[sl], self._invb_flat[sl], self._inv_cat[0][sl], self._inv_cat[1][sl], self._y_flat[sl]
+
+    def __getitem__(self, idx):
+        lo, hi = self._rows(idx)
+        ht, hb, hv, hs = self._history(lo, hi)
+        it, ib, iv, is_, ylab = self._inview(lo, hi)
+        lens = np.diff(self._inv_off[lo: hi + 1])
+        tm, bm = self.lookup_article_matrix, self.lookup_article_matrix_body
+        if self.eval_mode:
+            rep = lambda a: np.repeat(a, lens, axis=0)
+            his = (tm[rep(ht)], bm[rep(hb)], rep(hv)[:, :, None], rep(hs)[:, :, None])
+            pred = (tm[it][:, None, :], bm[ib][:, None, :], iv.reshape(-1, 1, 1), is_.reshape(-1, 1, 1))
+            return his + pred, ylab.reshape(-1, 1)
+        if len(lens) and lens.min() != lens.max():
+            raise ValueError("train mode needs equal-length in-view lists (sampling_strategy_wu2019); use eval_mode=True")
+        C = int(lens[0]) if len(lens) else 0
+        shape = (hi - lo, C)
+        his = (tm[ht], bm[hb], hv[:, :, None], hs[:, :, None])
+        pred = (tm[it.reshape(shape)], bm[ib.reshape(shape)], iv.reshape(shape)[:, :, None], is_.reshape(shape)[:, :, None])
+        return his + pred, ylab.reshape(shape)
+
+    def compact_eval_batch(self, idx):
+        """Eval batch without the per-candidate repetition of the history: (his_title (b,H,T), his_body (b,H,Tb),
+        his_vert (b,H,1), his_subvert (b,H,1), cand_title (n,T), cand_body (n,Tb), cand_vert (n,), cand_subvert (n,),
+        impression_of_row (n,), y (n, 1)), n = sum C_i.  Scores are identical to the repeated layout."""
+        lo, hi = self._rows(idx)
+        ht, hb, hv, hs = self._history(lo, hi)
+        it, ib, iv, is_, ylab = self._inview(lo, hi)
+        rows = np.repeat(np.arange(hi - lo, dtype=np.int32), np.diff(self._inv_off[lo: hi + 1]))
+        tm, bm = self.lookup_article_matrix, self.lookup_article_matrix_body
+        return (tm[ht], bm[hb], hv[:, :, None], hs[:, :, None], tm[it], bm[ib], iv, is_, rows, ylab.reshape(-1, 1))

@@ -1,9 +1,9 @@
-"""Hyper-parameter holders for the MI355X NRMS / NRMSDocVec / NPA / LSTUR path.
+"""Hyper-parameter holders for the MI355X NRMS / NRMSDocVec / NPA / LSTUR / NAML path.
 
 Same contract as the reference's ``model_config.py:82-114``: plain classes whose CLASS
 attributes are read by the model (``hparams.title_size`` ...) and may be overwritten in place
-by driver scripts (``ebnerd_nrms.py:85-96``); any attribute-bearing object works.  Only the
-model families on the hot path are provided (NAML is out of scope).
+by driver scripts (``ebnerd_nrms.py:85-96``); any attribute-bearing object works.  Every model family of the
+reference's ``ebrec.models.newsrec`` is provided.
 """
 from __future__ import annotations
 
@@ -93,5 +93,28 @@ class hparams_lstur(_OptimizerDefaults):
     type = "ini"
     attention_hidden_dim = 200
     gru_unit = 400
+    filter_num = 400
+    window_size = 3
+
+
+class hparams_naml(_OptimizerDefaults):
+    """reference model_config.py:23-42."""
+    __annotations__ = {
+        "title_size": int, "history_size": int, "body_size": int, "vert_num": int, "vert_emb_dim": int, "subvert_num": int,
+        "subvert_emb_dim": int, "dense_activation": str, "cnn_activation": str, "attention_hidden_dim": int, "filter_num": int,
+        "window_size": int, "optimizer": str, "loss": str, "dropout": float, "learning_rate": float,
+    }
+    # input dimensions
+    title_size = DEFAULT_TITLE_SIZE
+    history_size = 20
+    body_size = 40
+    vert_num = 100
+    vert_emb_dim = 10
+    subvert_num = 100
+    subvert_emb_dim = 10
+    # architecture
+    dense_activation = "relu"
+    cnn_activation = "relu"
+    attention_hidden_dim = 200
     filter_num = 400
     window_size = 3

@@ -1,0 +1,89 @@
+"""NAMLModel on MI355X: the reference's constructor-and-attribute surface (naml.py:13-369) over hand-written HIP kernels.
+
+    model = NAMLModel(hparams=hparams_naml, word2vec_embedding=emb, seed=42)
+    model.model.fit(train_loader, validation_data=val_loader, epochs=5)      # NAMLDataLoader batches
+    scores = model.scorer.predict(test_loader)                               # NAMLDataLoader(eval_mode=True)
+
+Inputs are the reference's eight arrays ``(his_input_title (B,H,T), his_input_body (B,H,Tb), his_input_vert (B,H,1),
+his_input_subvert (B,H,1), pred_input_title (B,C,T), pred_input_body (B,C,Tb), pred_input_vert (B,C,1),
+pred_input_subvert (B,C,1))`` (naml.py ``keras.Model([...8 inputs...], preds)``); the scorer takes C = 1.  Deliberate
+differences:
+  * one GPU, through libebnerd_hip.so only (RuntimeError otherwise -- no CPU fallback, no multi-rank form);
+  * dropout uses the build's counter-based stream, not TF's (statistical parity only);
+  * weights are saved as a named torch file (``model.model.save_weights``); TF weight lists are not imported.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ._engine import glorot_uniform_np
+from ._engine_naml import NAMLEngine
+from ._keras_like import ScorerModel, TrainModel
+
+
+class NAMLModel:
+    """NAML (Wu et al., IJCAI 2019): attentive multi-view news encoder -- CNN + additive attention over the title and over the
+    body, Dense views of the category and subcategory, additive attention over the four views -- and additive attention over
+    the clicked news as the user encoder (reference naml.py)."""
+
+    def __init__(self, hparams, word2vec_embedding: np.ndarray = None, word_emb_dim: int = 300, vocab_size: int = 32000,
+                 seed: int = None, *, n_users: int = 50000, train_embedding: bool = True, device=None, process_group=None,
+                 bce_on: str = "logits"):
+        self.hparams = hparams
+        self.n_users = n_users  # accepted and unused, as in the reference
+        self.seed = seed
+        if seed is not None:
+            np.random.seed(seed)
+            torch.manual_seed(seed)
+        if word2vec_embedding is None:
+            self.word2vec_embedding = glorot_uniform_np((vocab_size, word_emb_dim), seed)
+        else:
+            self.word2vec_embedding = word2vec_embedding
+        self._get_loss(hparams.loss)
+        self._get_opt(hparams.optimizer, hparams.learning_rate)
+        for attr in ("cnn_activation", "dense_activation"):
+            if getattr(hparams, attr, "relu") != "relu":
+                raise ValueError(f"{attr} {getattr(hparams, attr)!r}: the HIP Conv1D and categorical Dense implement relu")
+        self._engine = NAMLEngine(
+            np.asarray(self.word2vec_embedding), hparams.title_size, hparams.body_size, hparams.history_size, hparams.filter_num,
+            hparams.window_size, hparams.attention_hidden_dim, hparams.vert_num, hparams.vert_emb_dim, hparams.subvert_num,
+            hparams.subvert_emb_dim, hparams.dropout, hparams.learning_rate, hparams.loss, seed=seed,
+            train_embedding=train_embedding, device=device, process_group=process_group, bce_on=bce_on)
+        self.model, self.scorer = self._build_graph()
+
+    def _get_loss(self, loss: str):
+        if loss == "cross_entropy_loss":
+            return "categorical_crossentropy"
+        if loss == "log_loss":
+            return "binary_crossentropy"
+        raise ValueError(f"this loss not defined {loss}")
+
+    def _get_opt(self, optimizer: str, lr: float):
+        if optimizer == "adam":
+            return "adam"
+        raise ValueError(f"this optimizer not defined {optimizer}")
+
+    def _set_loss(self, loss: str):
+        self._get_loss(loss)
+        self._engine.loss = loss
+
+    def _build_graph(self):
+        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
+
+    # -- scorer bodies (naml.py: sigmoid(news(pred_one) . user)) -------------------------------------------------------------
+    def _score_pairs(self, *xs) -> torch.Tensor:
+        """sigmoid(cand_i . user_i) for every row i of the 8 scorer inputs (histories (N,H,.), candidates (N,1,.))."""
+        n = np.shape(xs[0])[0]
+        if np.shape(xs[4])[:2] != (n, 1):
+            raise ValueError(f"scorer expects one candidate per history row, got {np.shape(xs[0])} vs {np.shape(xs[4])}")
+        return self._engine.pair_scores(xs[:4], xs[4:8], np.arange(n), sigmoid=True)
+
+    def _score_compact(self, *xs) -> torch.Tensor:
+        """The same scores for the loader's compact eval layout: the 4 history arrays once per impression (b,H,.), the 4
+        candidate arrays (n,.), rows[i] = impression of candidate i."""
+        return self._engine.pair_scores(xs[:4], xs[4:8], np.asarray(xs[8]), sigmoid=True)
+
+    def train_step(self, *xs):
+        """One optimizer step on raw arrays (the 8 inputs and y); returns the batch loss (device tensor)."""
+        return self._engine.train_step(*xs)

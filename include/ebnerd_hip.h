@@ -705,6 +705,43 @@ int ebn_gru_fwd_f32(const float* gx, const float* X, const float* Wrec, const fl
 int ebn_gru_bwd_f32(const float* dhH, const float* X, const float* Wrec, const float* Hs, const float* act, float* dgx,
                     float* dgh, float* dh0, int64_t B, int32_t H, int32_t F, int32_t U, ebn_stream_t stream);
 
+/* ---- NAML (naml.py news encoder: title / body / vert / subvert views, layers.py:55-81 AttLayer2 over the views) -------------
+ * Title and body run ebn_gather_rows_f32 -> ebn_conv1d_fwd_f32 (pooling dropout p = 0) -> ebn_attpool_fwd_f32, with their own
+ * weights and the shared word table; the title at sites EBN_SITE_NEWS_IN / EBN_SITE_NPA_CONV, the body at the two sites below.
+ * The four views of an article are stacked view-major, Vw [n_views, N, F] (view v of article n at row v*N + n).           */
+#define EBN_SITE_NAML_BODY_IN 5
+#define EBN_SITE_NAML_BODY_CONV 6
+
+/* Both categorical views (naml.py _build_vertencoder / _build_subvertencoder) in one launch, view i = 0, 1:
+ *   out_i[n, f] = relu(sum_k table_i[ids_i[n], k] Wb_i[k, f] + Wb_i[K_i, f])   (n < N, f < F; out_i [N, F], e.g. Vw[2], Vw[3])
+ * table_i [rows_i, K_i] the Embedding, Wb_i [K_i + 1, F] the Dense kernel rows then its bias row.  K_i <= 256, any value (no
+ * multiple-of-4 rule; the contraction runs on the VALU, k ascending).  An id outside [0, rows_i) reads a zero row and sets
+ * *oob_flag (may be NULL) to 1.  No alignment requirement.                                                                   */
+int ebn_naml_catview_fwd_f32(const int32_t* ids0, const float* table0, int64_t rows0, int32_t K0, const float* Wb0,
+                             float* out0, const int32_t* ids1, const float* table1, int64_t rows1, int32_t K1,
+                             const float* Wb1, float* out1, int64_t N, int32_t F, int32_t* oob_flag, ebn_stream_t stream);
+/* Its backward from dout_i [N, F] and the forward's out_i (ReLU gate out > 0): dWb_i [K_i + 1, F] (kernel rows, then the bias
+ * row) and the dense table gradient dtable_i [rows_i, K_i] (rows no id names get 0; ids outside the table contribute
+ * nothing), all overwritten.  Two launches: per slice of 32 articles the partial [dW ; db] and de = dY.W^T, then the slices
+ * summed in ascending order and, for each table row, the de of the articles naming it in ascending article order -- no
+ * atomics, the same bits on every run.  partials: ebn_naml_catview_partials_len(N, K0, K1, F) floats of scratch.            */
+int64_t ebn_naml_catview_partials_len(int64_t N, int32_t K0, int32_t K1, int32_t F);
+int ebn_naml_catview_bwd_f32(const int32_t* ids0, const float* table0, int64_t rows0, int32_t K0, const float* Wb0,
+                             const float* out0, const float* dout0, float* dWb0, float* dtable0, const int32_t* ids1,
+                             const float* table1, int64_t rows1, int32_t K1, const float* Wb1, const float* out1,
+                             const float* dout1, float* dWb1, float* dtable1, float* partials, int64_t partials_len,
+                             int64_t N, int32_t F, ebn_stream_t stream);
+/* AttLayer2 over the n_views (<= 8) strided rows of each article, one wave per article (the view-level attention of naml.py):
+ *   U <- tanh(U + b) in place ([n_views*N, A], U = Vw.Wa from one ebn_gemm_f32 over the n_views*N rows);
+ *   a_v = exp(U_v . q) (no max-subtraction);  w_v = a_v / (sum_v a + 1e-7) -> w [n_views, N];  news [N, F] = sum_v w_v Vw[v, n]. */
+int ebn_naml_viewatt_fwd_f32(float* U, const float* b, const float* q, const float* Vw, float* w, float* news, int64_t N,
+                             int32_t n_views, int32_t F, int32_t A, ebn_stream_t stream);
+/* Its backward's direct part from dnews [N, F]: dVw[v, n] = w_v dnews_n (overwritten; must not alias Vw) and
+ * de [n_views, N] = w_v (dw_v - sum_u w_u dw_u), dw_v = dnews_n . Vw[v, n].  The rest is row-order agnostic and reuses
+ * ebn_attpool_bwd_dpre_f32 over the n_views*N rows (dpre, dq, db) and ebn_gemm_f32 (dWa = Vw^T.dpre, dVw += dpre.Wa^T).      */
+int ebn_naml_viewatt_bwd_f32(const float* Vw, const float* w, const float* dnews, float* dVw, float* de, int64_t N,
+                             int32_t n_views, int32_t F, ebn_stream_t stream);
+
 /* Step prologue: copy up to three device buffers (history ids, candidate ids, labels of a batch handed over as device
  * tensors -- the inputs of nrms.py:170-176) into the step's static buffers with ONE launch; n_i in bytes, multiples
  * of 4; a NULL source or n_i = 0 skips that pair.                                                                   */
