@@ -5,6 +5,7 @@
 // Work items are 16-byte vectors; consecutive lanes take consecutive vectors of a row so a
 // wave covers whole 128-B lines of the (V x D) table; each thread keeps GATHER_UNROLL independent
 // row loads in flight before the first store (random rows -> latency-bound otherwise).
+#include "ebn_adam_flat.h"
 #include "ebn_common.h"
 
 namespace {
@@ -160,13 +161,10 @@ __global__ __launch_bounds__(256) void adam_keras_fixed_kernel(float* __restrict
                                                                int32_t* __restrict__ range_flag) {
   const float alpha = st->adam_alpha;
   bool bad = false;
-#define EBN_ADAMQ(T, Q, M, V)                                                                    \
-  {                                                                                              \
-    const float gg = static_cast<float>(static_cast<double>(Q) * (1.0 / FIXED_SCALE)) * gscale; \
-    (M) = (M) + (gg - (M)) * omb1;                                                               \
-    (V) = (V) + (gg * gg - (V)) * omb2;                                                          \
-    (T) = (T) - alpha * (M) / (sqrtf(V) + eps);                                                  \
-    bad |= (Q) >= FIXED_SUM_MAX || (Q) <= -FIXED_SUM_MAX;                                        \
+#define EBN_ADAMQ(T, Q, M, V)                                                                                                      \
+  {                                                                                                                                \
+    ebn_adam_element((T), static_cast<float>(static_cast<double>(Q) * (1.0 / FIXED_SCALE)), (M), (V), alpha, omb1, omb2, eps, gscale); \
+    bad |= (Q) >= FIXED_SUM_MAX || (Q) <= -FIXED_SUM_MAX;                                                                          \
   }
   const int64_t n4 = n / 4;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += static_cast<int64_t>(gridDim.x) * 256) {

@@ -1131,15 +1131,17 @@ __global__ __launch_bounds__(T * T / 4) void gemm_small_tn_finale_kernel(SmallGr
   const EbnTnFinale& f = gf.f;
   const int nwg = gridDim.x, tid = threadIdx.x, b = xcd_chunked_tile(blockIdx.x, nwg);
   constexpr int NT = T * T / 4;
-  int i = 0;
-  while (i + 1 < g.n && b >= g.first[i + 1]) ++i;
-  const SmallProblem& p = g.p[i];
-  GemmEpi epi{nullptr, nullptr, 0, 1, nullptr};
-  epi.colsum = g.colsum[i];
-  epi.l2w = g.l2w[i];
-  epi.two_lambda = g.two_lambda[i];
-  const int t = b - g.first[i];
-  small_vec_body<true, false, T, true>(p.M, p.N, p.K, p.alpha, p.A, p.lda, p.B, p.ldb, p.beta, p.C, p.ldc, epi, t % p.tiles_x, t / p.tiles_x, &f);
+  if (b < g.first[g.n]) {  // (block-uniform) workgroups past the last tile exist only for the head's finishing blocks (see the launch)
+    int i = 0;
+    while (i + 1 < g.n && b >= g.first[i + 1]) ++i;
+    const SmallProblem& p = g.p[i];
+    GemmEpi epi{nullptr, nullptr, 0, 1, nullptr};
+    epi.colsum = g.colsum[i];
+    epi.l2w = g.l2w[i];
+    epi.two_lambda = g.two_lambda[i];
+    const int t = b - g.first[i];
+    small_vec_body<true, false, T, true>(p.M, p.N, p.K, p.alpha, p.A, p.lda, p.B, p.ldb, p.beta, p.C, p.ldc, epi, t % p.tiles_x, t / p.tiles_x, &f);
+  }
   const float al = f.adam.st->adam_alpha;
   // element-wise Adam over the remaining ranges: the concatenated index space, one contiguous share per workgroup
   {
@@ -1634,14 +1636,16 @@ int ebn_tn_group_finale_launch(const ebn_tn_problem* problems, int32_t n, const 
     EBN_REQUIRE(total < (int64_t{1} << 30), EBN_ERR_UNSUPPORTED);
   }
   g.first[n] = static_cast<int32_t>(total);
-  EBN_REQUIRE(total >= (2 * fin.A + 255) / 256 + 1, EBN_ERR_UNSUPPORTED);  // the head's finishing blocks ride on the first workgroups
+  // the head's finishing blocks ride on the first workgroups: a group with fewer tiles than that launches the difference as
+  // workgroups without a tile (at most ceil(2A / 256) of them -- a model whose Dense kernels are smaller than its AttLayer2)
+  const int64_t nh = (2 * static_cast<int64_t>(fin.A) + 255) / 256 + 1, nwg = total > nh ? total : nh;
 #define EBN_TN_FINALE(TT)                                                                                                         \
   do {                                                                                                                            \
     constexpr size_t lds = static_cast<size_t>(2) * 2 * (TT) * SLV * sizeof(float);                                               \
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_small_tn_finale_kernel<TT>),           \
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));        \
     if (attr != hipSuccess) return static_cast<int>(attr);                                                                        \
-    EBN_LAUNCH(gemm_small_tn_finale_kernel<TT>, dim3(static_cast<unsigned>(total)), dim3((TT) * (TT) / 4), lds, s, gf);           \
+    EBN_LAUNCH(gemm_small_tn_finale_kernel<TT>, dim3(static_cast<unsigned>(nwg)), dim3((TT) * (TT) / 4), lds, s, gf);             \
   } while (0)
   if (T == 64) EBN_TN_FINALE(64);
   else EBN_TN_FINALE(32);

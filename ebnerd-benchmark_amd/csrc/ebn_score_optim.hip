@@ -4,6 +4,7 @@
 // device state.  All latency- or HBM-bound elementwise/row work.
 #include <atomic>
 
+#include "ebn_adam_flat.h"
 #include "ebn_common.h"
 
 namespace {
@@ -271,31 +272,23 @@ __global__ __launch_bounds__(256) void adam_keras_kernel(float* __restrict__ the
   const float4* g4 = reinterpret_cast<const float4*>(g);
   float4* m4 = reinterpret_cast<float4*>(m);
   float4* v4 = reinterpret_cast<float4*>(v);
-#define EBN_ADAM1(T, G, M, V)                 \
-  {                                           \
-    const float gg = (G) * gscale;            \
-    (M) = (M) + (gg - (M)) * omb1;            \
-    (V) = (V) + (gg * gg - (V)) * omb2;       \
-    (T) = (T) - alpha * (M) / (sqrtf(V) + eps); \
-  }
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += stride) {
     float4 t = t4[i], gr = g4[i], mm = m4[i], vv = v4[i];
-    EBN_ADAM1(t.x, gr.x, mm.x, vv.x)
-    EBN_ADAM1(t.y, gr.y, mm.y, vv.y)
-    EBN_ADAM1(t.z, gr.z, mm.z, vv.z)
-    EBN_ADAM1(t.w, gr.w, mm.w, vv.w)
+    ebn_adam_element(t.x, gr.x, mm.x, vv.x, alpha, omb1, omb2, eps, gscale);
+    ebn_adam_element(t.y, gr.y, mm.y, vv.y, alpha, omb1, omb2, eps, gscale);
+    ebn_adam_element(t.z, gr.z, mm.z, vv.z, alpha, omb1, omb2, eps, gscale);
+    ebn_adam_element(t.w, gr.w, mm.w, vv.w, alpha, omb1, omb2, eps, gscale);
     t4[i] = t;
     m4[i] = mm;
     v4[i] = vv;
   }
   for (int64_t i = n4 * 4 + static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) {
     float t = theta[i], mm = m[i], vv = v[i];
-    EBN_ADAM1(t, g[i], mm, vv)
+    ebn_adam_element(t, g[i], mm, vv, alpha, omb1, omb2, eps, gscale);
     theta[i] = t;
     m[i] = mm;
     v[i] = vv;
   }
-#undef EBN_ADAM1
 }
 
 __global__ __launch_bounds__(256) void adam_keras_scalar_kernel(float* __restrict__ theta,
@@ -306,12 +299,11 @@ __global__ __launch_bounds__(256) void adam_keras_scalar_kernel(float* __restric
   const float alpha = st->adam_alpha;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n;
        i += static_cast<int64_t>(gridDim.x) * 256) {
-    const float gg = g[i] * gscale;
-    const float mm = m[i] + (gg - m[i]) * omb1;
-    const float vv = v[i] + (gg * gg - v[i]) * omb2;
+    float t = theta[i], mm = m[i], vv = v[i];
+    ebn_adam_element(t, g[i], mm, vv, alpha, omb1, omb2, eps, gscale);
     m[i] = mm;
     v[i] = vv;
-    theta[i] = theta[i] - alpha * mm / (sqrtf(vv) + eps);
+    theta[i] = t;
   }
 }
 

@@ -884,11 +884,12 @@ class NRMSEngine(StagingMixin, SegmentsMixin):
             labels = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(y, dtype=np.float32))))
             nb.labels[: B * C].copy_(labels.reshape(-1).to(device=self.device, dtype=torch.float32), non_blocking=True)
         if self.use_graph and self.graph_capable:
-            run = self._graphs.get((B, C, advanced))
+            key = self._graph_key(B, C, advanced)
+            run = self._graphs.get(key)
             if run is None:
                 run = self._capture(B, C, advanced)
             if self.trace is not None:
-                self.trace.run(run, self._graph_desc.get((B, C, advanced), []))
+                self.trace.run(run, self._graph_desc.get(key, []))
             else:
                 for fn in run:
                     fn()

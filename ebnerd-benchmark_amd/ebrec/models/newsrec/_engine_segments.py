@@ -121,11 +121,17 @@ class SegmentsMixin:
         self._graphs.clear()
         return self.graph_collectives
 
+    def _graph_key(self, B, C, advanced=False):
+        """a captured step freezes its launch form: the flags that choose it are part of the key, so that changing one between steps
+        captures the new form instead of replaying the old one"""
+        return (B, C, advanced, bool(self.adam_in_finish), bool(self.defer_finish), bool(self.multi))
+
     def _capture(self, B, C, advanced=False):
         """Runs of kernel-only segments become hipGraphs; collectives stay eager launches between the replays."""
         torch.cuda.synchronize()
+        key = self._graph_key(B, C, advanced)
         segs, run, pool, i = self._segments(B, C, advanced), [], None, 0
-        desc = self.__dict__.setdefault("_graph_desc", {}).setdefault((B, C, advanced), [])
+        desc = self.__dict__.setdefault("_graph_desc", {}).setdefault(key, [])
         desc.clear()
         if self.graph_collectives and self.multi:
             # the collectives are captured too (RCCL supports stream capture): the whole multi-rank step is ONE graph, no
@@ -135,9 +141,9 @@ class SegmentsMixin:
                 for _kind, fn in segs:
                     fn()
             self._graph_objs = getattr(self, "_graph_objs", []) + [g]
-            self._graphs[(B, C, advanced)] = [g.replay]
+            self._graphs[key] = [g.replay]
             desc.append("ONE hipGraph: " + " | ".join(self.SEG_KINDS[k] for k, _fn in segs))
-            return self._graphs[(B, C, advanced)]
+            return self._graphs[key]
         while i < len(segs):
             if segs[i][0] != "k":  # "c" | "a" | "w": collectives (and the wait for them) stay eager launches between the replays
                 run.append(segs[i][1])
@@ -156,7 +162,7 @@ class SegmentsMixin:
             desc.append(f"hipGraph replay of kernel segments {i}..{j - 1} of the step's {len(segs)}")
             self._graph_objs = getattr(self, "_graph_objs", []) + [g]
             i = j
-        self._graphs[(B, C, advanced)] = run
+        self._graphs[key] = run
         return run
 
     def _segments(self, B, C, advanced=False):

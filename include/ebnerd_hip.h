@@ -593,8 +593,9 @@ int ebn_gemm_tn_group_f32(const ebn_tn_problem* problems, int32_t n, ebn_stream_
  * (2) the user head's finishing sums (ebn_user_head_train_f32 called with dq == db == NULL leaves `head_partials`, `loss_rows`):
  * d(q), d(b) over the B impressions and loss_out[0] = sum(loss_rows) + l2 * sum_l sum(W[l]^2) (ebn_dvn_bwd_f32 called with
  * args->loss == NULL leaves the L2 term to this call), then Adam on d(q) / d(b).  Same arithmetic, element by element, as
- * ebn_gemm_tn_group_f32 + ebn_user_head_train_f32's finishing pass + ebn_adam_keras_step_f32.  With world > 1 the gradient all-reduce
- * sits between the gradients and Adam: the separate calls stay.                                                                       */
+ * ebn_gemm_tn_group_f32 + ebn_user_head_train_f32's finishing pass + ebn_adam_keras_step_f32 (one Adam element, ebn_adam_flat.h: the
+ * same bits).  Any tile count: a group with fewer tiles than the head's ceil(2A / 256) + 1 finishing blocks launches the difference as
+ * workgroups without a tile.  With world > 1 the gradient all-reduce sits between the gradients and Adam: the separate calls stay.      */
 #define EBN_DVN_FINALE_MAX_REST 12
 typedef struct ebn_dvn_finale {
   float* theta;

@@ -67,12 +67,37 @@ def test_forward_eval_mode_uses_moving_statistics(docvec, cfg):
     assert_close(ne, want, rtol=2e-5, atol=2e-5, what="docvec newsencoder")
 
 
+def check_first_step_against_oracle(m, hp, P, his, pred, y, seed, got, extra=()):
+    """The loss, the gradients and the moving statistics of a model's FIRST training step (from the weights P) against the float64 oracle;
+    `extra`: parameters checked beyond the ones every configuration has."""
+    eng, B = m._engine, his.shape[0]
+    p, l2, units = hp.dropout, hp.newsencoder_l2_regularization, hp.newsencoder_units_per_layer
+    gate = ReluTieGate(eng, B * hp.history_size, B * pred.shape[1])  # ReLU inputs within rounding of 0: the engine's side (order-independent comparison)
+    L, _, g, stats = on.docvec_loss_and_grads(his.astype(np.float64), pred.astype(np.float64), y, P, hp.head_num, hp.head_dim,
+                                              l2=l2, training=True, drop=on.Drop(p, seed, 1) if p > 0 else None, relu_gate=gate)
+    assert gate.fraction() < 1e-3, (gate.n_ambiguous, gate.n_total)  # (small shapes: one element of 3 x 12 x 36 would already be 8e-4)
+    assert abs(got - L) <= 3e-5 * max(1.0, abs(L)), (got, L)
+    nl = len(units)
+    for k in [f"d{l}_{s}" for l in range(nl) for s in ("W", "b")] + [f"bn{l}_{s}" for l in range(nl) for s in ("g", "b")] + ["out_W", "out_b", "u_W", "u_b", *extra]:
+        want = g[k].reshape(eng.params.shapes[k])
+        assert_close(eng.params.g(k).cpu().numpy(), want, rtol=2e-4, atol=1e-6 + 2e-4 * np.abs(want).max(), what=f"d{k}")
+    want = np.concatenate([g["u_WQ"], g["u_WK"], g["u_WV"]], 1)
+    assert_close(eng.params.g("u_Wqkv").cpu().numpy(), want, rtol=2e-4, atol=1e-6 + 2e-4 * np.abs(want).max(), what="du_Wqkv")
+    Pn = dict(P)
+    on.bn_update_moving(Pn, stats)  # history call site first, then candidates: two updates per step
+    for l in range(nl):
+        assert_close(eng.bn_mean[l].cpu().numpy(), Pn[f"bn{l}_mean"], rtol=1e-5, atol=1e-6, what=f"moving mean {l}")
+        assert_close(eng.bn_var[l].cpu().numpy(), Pn[f"bn{l}_var"], rtol=1e-5, atol=1e-6, what=f"moving var {l}")
+
+
 @pytest.mark.parametrize("fused", [True, False], ids=["fused_launches", "separate_passes"])
-@pytest.mark.parametrize("units,din,B", [([48, 40], 64, 8), ([200, 136, 72], 300, 24), ([36], 20, 3)])
+@pytest.mark.parametrize("units,din,B", [([48, 40], 64, 8), ([200, 136, 72], 300, 24), ([36], 20, 3),
+                                         ([4], 20, 3), ([260, 68], 96, 8), ([64, 48, 40, 36], 64, 8), ([1024], 100, 4)])
 @pytest.mark.parametrize("p,l2", [(0.0, 0.0), (0.2, 1e-4)])
 def test_train_step_gradients_loss_and_moving_stats(docvec, p, l2, units, din, B, fused):
     """Both forms of the news encoder's training step -- BatchNormalization / Dropout / ReLU-backward inside the Dense launches
-    (csrc/ebn_docvec.hip; partial row tiles, partial and multiple 128-deep slabs, 1-3 hidden layers) and as separate passes."""
+    (csrc/ebn_docvec.hip; partial row tiles, partial and multiple 128-deep slabs) and as separate passes -- up to the edges of what the
+    fused launches take: 1-4 hidden layers, widths from 4 to MAX_K = 1024, widths that are not multiples of 64 above 256."""
     hp = make_hp(title_size=din, newsencoder_units_per_layer=units, head_num=4, head_dim=8, attention_hidden_dim=12,
                  history_size=7, dropout=p, newsencoder_l2_regularization=l2)
     seed = 5
@@ -83,25 +108,78 @@ def test_train_step_gradients_loss_and_moving_stats(docvec, p, l2, units, din, B
     rng = np.random.default_rng(2)
     his, pred, y = data(rng, B, hp.history_size, 5, hp.title_size)
     got = float(m.train_step(his, pred, y).item())
+    assert (m._engine._bufs["mlp"].get("dvn_live") is not None) == fused
+    check_first_step_against_oracle(m, hp, P, his, pred, y, seed, got)
+
+
+@pytest.mark.parametrize("units", [[1028], [30]], ids=["wider_than_max_k", "not_a_multiple_of_4"])
+def test_a_news_mlp_just_outside_the_fused_gate_trains_with_the_separate_passes(docvec, units):
+    """ebn_dvn_supported refuses a hidden width above MAX_K = 1024 or not a multiple of 4: the step runs the separate passes and the
+    separate Adam launch.  The finale's own gate (`_finale_live`) still says yes -- the step must not half-take it: no fused launch, the
+    optimizer exactly once (the weights after the step = one float64 Adam step on the step's own gradients), the oracle's gradients."""
+    hp = make_hp(title_size=64, newsencoder_units_per_layer=units, head_num=2, head_dim=16, attention_hidden_dim=12, history_size=7)
+    seed = 5
+    P = oracle_params(hp, 9)
+    m = docvec(hp, seed=seed)
+    m.model.set_weights(weight_list(P))
     eng = m._engine
-    gate = ReluTieGate(eng, B * hp.history_size, B * 5)  # ReLU inputs within rounding of 0: the engine's side (order-independent comparison)
-    L, _, g, stats = on.docvec_loss_and_grads(his.astype(np.float64), pred.astype(np.float64), y, P, hp.head_num, hp.head_dim,
-                                              l2=l2, training=True, drop=on.Drop(p, seed, 1) if p > 0 else None, relu_gate=gate)
-    assert gate.fraction() < 1e-3, (gate.n_ambiguous, gate.n_total)  # (small shapes: one element of 3 x 12 x 36 would already be 8e-4)
-    assert abs(got - L) <= 3e-5 * max(1.0, abs(L)), (got, L)
-    E = eng.E
-    assert (eng._bufs["mlp"].get("dvn_live") is not None) == fused
-    nl = len(units)
-    for k in [f"d{l}_{s}" for l in range(nl) for s in ("W", "b")] + [f"bn{l}_{s}" for l in range(nl) for s in ("g", "b")] + ["out_W", "out_b", "u_W", "u_b"]:
-        want = g[k].reshape(eng.params.shapes[k])
-        assert_close(eng.params.g(k).cpu().numpy(), want, rtol=2e-4, atol=1e-6 + 2e-4 * np.abs(want).max(), what=f"d{k}")
-    want = np.concatenate([g["u_WQ"], g["u_WK"], g["u_WV"]], 1)
-    assert_close(eng.params.g("u_Wqkv").cpu().numpy(), want, rtol=2e-4, atol=1e-6 + 2e-4 * np.abs(want).max(), what="du_Wqkv")
-    Pn = dict(P)
-    on.bn_update_moving(Pn, stats)  # history call site first, then candidates: two updates per step
-    for l in range(nl):
-        assert_close(eng.bn_mean[l].cpu().numpy(), Pn[f"bn{l}_mean"], rtol=1e-5, atol=1e-6, what=f"moving mean {l}")
-        assert_close(eng.bn_var[l].cpu().numpy(), Pn[f"bn{l}_var"], rtol=1e-5, atol=1e-6, what=f"moving var {l}")
+    assert eng.fuse_news_mlp and eng.fuse_finale and eng._finale_live(5)
+    theta0 = eng.params.data.cpu().numpy().astype(np.float64)
+    rng = np.random.default_rng(2)
+    B = 8
+    his, pred, y = data(rng, B, hp.history_size, 5, hp.title_size)
+    got = float(m.train_step(his, pred, y).item())
+    mb = eng._bufs["mlp"]
+    assert mb.get("dvn_live") is None and eng._dvn(mb, B * hp.history_size, B * 5) is None
+    assert not eng._step_applied_adam(mb) and int(eng.read_state().step) == 1
+    check_first_step_against_oracle(m, hp, P, his, pred, y, seed, got, extra=("u_q",))
+    g = eng.params.grad.cpu().numpy().astype(np.float64)
+    mm, vv = np.zeros_like(theta0), np.zeros_like(theta0)
+    on.adam_keras_step(theta0, g, mm, vv, 1, lr=hp.learning_rate)
+    assert_close(eng.params.data.cpu().numpy(), theta0, rtol=1e-5, atol=2e-6, what="weights after one step")
+    assert_close(eng.params.m.cpu().numpy(), mm, rtol=1e-5, atol=1e-9, what="Adam m after one step")
+
+
+@pytest.mark.parametrize("graphs", [False, True], ids=["eager", "graphs"])
+@pytest.mark.parametrize("A", [128, 129, 132, 200])
+def test_the_one_launch_finale_takes_fewer_tiles_than_the_head_has_finishing_blocks(docvec, A, graphs):
+    """Round-6 ADVICE (medium): the finale deals the head's ceil(2A / 256) + 1 finishing blocks over the workgroups of the weight-gradient
+    tiles.  A model whose Dense kernels are small next to its AttLayer2 -- title_size 32, units [32], E = 32: two 32 x 32 tiles -- needs 2
+    blocks at A = 128 but 3 at A = 132 and at the default A = 200, and its every step raised HipError.  Now the launch adds the missing
+    workgroups: the first step against the float64 oracle (d(q) and d(b) included), three steps bit-identical to the separate launches.
+    (A = 129: the one-launch head takes multiples of 4 only, so the step keeps the separate launches -- and must still train correctly.)"""
+    import torch
+
+    hp = make_hp(title_size=32, newsencoder_units_per_layer=[32], head_num=2, head_dim=16, attention_hidden_dim=A, history_size=7)
+    seed, B = 5, 8
+    P = oracle_params(hp, 9)
+    rng = np.random.default_rng(2)
+    batches = [data(rng, B, hp.history_size, 5, hp.title_size) for _ in range(3)]
+    out = []
+    for finale in (True, False):
+        m = docvec(hp, seed=seed)
+        m.model.set_weights(weight_list(P))
+        eng = m._engine
+        eng.fuse_finale = finale
+        eng.enable_graphs(graphs)
+        live = finale and A % 4 == 0
+        assert eng._finale_live(5) == live
+        losses, g1 = [], None
+        for i, bt in enumerate(batches):
+            losses.append(float(m.train_step(*bt).item()))
+            assert eng._step_applied_adam(eng._bufs["mlp"]) == live
+            if i == 0:
+                check_first_step_against_oracle(m, hp, P, *bt, seed, losses[0], extra=("u_q",))
+                g1 = eng.params.grad.cpu().numpy().copy()
+        torch.cuda.synchronize()
+        out.append((losses, g1, eng.params.data.cpu().numpy().copy(), eng.params.m.cpu().numpy().copy(),
+                    eng.params.v.cpu().numpy().copy(), [t.cpu().numpy().copy() for t in eng.bn_mean + eng.bn_var], int(eng.read_state().step)))
+    a, b = out
+    assert a[0] == b[0], (a[0], b[0])
+    assert a[6] == b[6] == 3
+    for x, y, what in zip(a[1:5], b[1:5], ("first-step gradients", "weights", "Adam m", "Adam v")):
+        assert np.array_equal(x, y), what
+    assert all(np.array_equal(x, y) for x, y in zip(a[5], b[5]))
 
 
 def test_docvec_fit_surface_and_weights_roundtrip(docvec, tmp_path):
@@ -254,15 +332,15 @@ def test_the_one_launch_finale_equals_the_three_launches_it_replaces(docvec, uni
         out.append((losses, g1, eng.params.data.cpu().numpy().copy(), eng.params.m.cpu().numpy().copy(),
                     eng.params.v.cpu().numpy().copy(), [t.cpu().numpy().copy() for t in eng.bn_mean + eng.bn_var], int(eng.read_state().step)))
     a, b = out
-    # the loss: same rows, same fixed-order sums, same L2 term -- bit-identical on the first step; later steps start from weights that
-    # agree to an ulp (the compiler contracts the two Adam kernels' arithmetic differently), so their losses agree to ~1e-7
-    assert a[0][0] == b[0][0] and np.allclose(a[0], b[0], rtol=2e-6, atol=0), (a[0], b[0])
+    # the loss: same rows, same fixed-order sums, same L2 term; Adam: one element function (csrc/ebn_adam_flat.h) whose rounding is fixed
+    # in the source -- so every step starts from the same weights and all three are bit-identical
+    assert a[0] == b[0], (a[0], b[0])
     assert a[6] == b[6] == 3
     assert np.array_equal(a[1], b[1])  # every gradient of the first step (same weights going in): the same bits
-    for x, y, what in zip(a[2:5], b[2:5], ("weights", "Adam m", "Adam v")):  # (steps 2 and 3 start from weights an ulp apart: their gradients agree to ~1e-4)
-        assert_close(x, y, rtol=1e-4, atol=1e-8 + 2e-4 * np.abs(y).max(), what=f"finale vs separate launches after three steps: {what}")
+    for x, y, what in zip(a[2:5], b[2:5], ("weights", "Adam m", "Adam v")):
+        assert np.array_equal(x, y), f"finale vs separate launches after three steps: {what}"
     for x, y in zip(a[5], b[5]):
-        assert_close(x, y, rtol=1e-5, atol=1e-7, what="moving statistics")
+        assert np.array_equal(x, y), "moving statistics"
 
 
 def test_fused_column_sums_outside_the_fixed_point_range_raise_instead_of_wrapping(docvec):

@@ -1321,15 +1321,24 @@ def test_finishing_launch_with_adam_inside_against_float64(hip):
     assert hip.lib().ebn_grad_finish_adam_f32(jobs, 3, ctypes.byref(bad), P(st), S()) == -1  # no buffers
 
 
-@pytest.mark.parametrize("shapes", [[(48, 40, 96), (20, 36, 96)], [(768, 512, 800), (512, 512, 800), (512, 512, 800), (512, 256, 800)]])
-def test_docvec_finale_against_float64(hip, shapes):
+_FINALE_SHAPES = [[(48, 40, 96), (20, 36, 96)], [(768, 512, 800), (512, 512, 800), (512, 512, 800), (512, 256, 800)], [(32, 32, 64), (32, 32, 64)]]
+
+
+@pytest.mark.parametrize("shapes,A_", [pytest.param(s, a, id=f"shapes{i}" + ("" if a == 24 else f"-A{a}"))
+                                       for i, s in enumerate(_FINALE_SHAPES) for a in (24, 128, 129, 200, 300)])
+def test_docvec_finale_against_float64(hip, shapes, A_):
     """ebn_dvn_finale_f32 at the kernel level: the grouped weight gradients (+ column sums + L2 term) written into a flat gradient buffer,
     Adam on them in the tiles' epilogues, Adam over a `rest` range, the head's d(q) / d(b) sums + Adam, and the batch loss = sum(loss rows)
-    + l2 * sum of the L2 column-tile sums the forward launches leave in `stat` -- all against float64 (32 x 32 and 64 x 64 tiles)."""
+    + l2 * sum of the L2 column-tile sums the forward launches leave in `stat` -- all against float64 (32 x 32 and 64 x 64 tiles).
+    The head's finishing takes ceil(2A / 256) + 1 blocks (the sums of 256 entries each, then the loss): 2 up to A = 128, more above.  The
+    two-tile group has FEWER tiles than that at A = 129 / 200 (nh - 1) and 300 (nh - 2) -- the launch must still run every finishing block."""
     from ebrec import _hip
 
     rng = np.random.default_rng(11 + len(shapes))
-    A_, B_ = 24, 7
+    B_ = 7
+    nh = -(-2 * A_ // 256) + 1  # the head's finishing blocks
+    if shapes[0] == (32, 32, 64):  # two 32 x 32 tiles
+        assert (2 < nh) == (A_ > 128) and (A_ not in (129, 200) or nh == 3)
     segs = {}
     for i, (M, N, K) in enumerate(shapes):
         segs[f"W{i}"], segs[f"b{i}"] = M * N, N
@@ -1379,6 +1388,8 @@ def test_docvec_finale_against_float64(hip, shapes):
     hip.call("ebn_step_advance", P(st), 0.9, 0.999, S())
     hip.call("ebn_dvn_finale_f32", ctypes.byref(a), probs, len(shapes), ctypes.byref(f), P(st), S())
     owned = g != 0
+    head = np.r_[offs["uq"]: offs["uq"] + A_, offs["ub"]: offs["ub"] + A_]
+    assert owned[head].all()  # all 2A entries of d(q) / d(b), and their Adam updates, are among the checked elements
     assert_close(host(g_d)[owned], g[owned], rtol=2e-5, atol=2e-5 * np.abs(g).max(), what="gradients")
     want_loss = rows.astype(np.float64).sum() + 0.01 * sum(float(x.astype(np.float64).sum()) for x in l2_vals)
     assert abs(float(loss.item()) - want_loss) < 1e-5 * max(1.0, abs(want_loss))
