@@ -42,6 +42,15 @@ def repeat_by_list_values_from_matrix(input_array, matrix: np.ndarray, repeats) 
     return np.repeat(matrix[np.asarray(input_array)], repeats=np.asarray(repeats), axis=0)
 
 
+def convert_to_nested_list(lst, sublist_size: int):
+    """Consecutive sublists of `sublist_size` elements (reference _python.py:359-367).
+
+    >>> convert_to_nested_list([0, 0, 1, 1, 0, 0], 3)
+    [[0, 0, 1], [1, 0, 0]]
+    """
+    return [lst[i: i + sublist_size] for i in range(0, len(lst), sublist_size)]
+
+
 def rank_predictions_by_score(arr: Iterable[float]) -> np.ndarray:
     """1 for the highest score, 2 for the next, ... (reference _python.py:41-59)."""
     return np.argsort(np.argsort(arr)[::-1]) + 1

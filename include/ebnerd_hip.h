@@ -743,6 +743,77 @@ int ebn_naml_viewatt_fwd_f32(float* U, const float* b, const float* q, const flo
 int ebn_naml_viewatt_bwd_f32(const float* Vw, const float* w, const float* dnews, float* dVw, float* de, int64_t N,
                              int32_t n_views, int32_t F, ebn_stream_t stream);
 
+/* ---- Fastformer (reference models/fastformer/fastformer.py; PyTorch, BERT-style blocks around additive attention) ---------------
+ * The Linear layers run on ebn_gemm_f32 (torch's [out, in] weights through transB = 1); these entry points are everything between
+ * them.  Exact fp32, fixed summation orders, no float atomics.  Dropout: the counter stream of ebn_step_advance's keys, but the
+ * key of a call site is passed BY VALUE (`drop_key`; drop_p = 0 disables it): this model's 1 + 2 * layers sites do not live in
+ * ebn_step_state.  The mask of element (r, c) is that of flat index r * D + c.
+ *
+ * bias + dropout + residual + LayerNorm over R rows of D <= 1024 columns:
+ *   mode 0 (SequenceFastformerEncoder.forward): Y = drop(LN(X + bias + res)), res [D] one row broadcast to every row;
+ *   mode 1 (BertSelfOutput / BertOutput):       Y = LN(drop(X + bias) + res), res [R, D];
+ *   LN(z) = gamma * xhat + beta, xhat = (z - mean) / sqrt(var + eps), biased variance.  xhat [R, D] and rstd [R] are what the
+ *   backward needs (both may be NULL: inference).  Y may alias X.                                                           */
+int ebn_ff_ln_fwd_f32(const float* X, const float* bias, const float* res, const float* gamma, const float* beta, float eps,
+                      int32_t mode, uint32_t drop_key, float drop_p, float* Y, float* xhat, float* rstd, int64_t R, int32_t D,
+                      ebn_stream_t stream);
+/* Its backward from dY: dX [R, D] = dL/dX; mode 1 also dres [R, D] = dL/dres.  The column sums are left as *n_parts (a HOST
+ * out-parameter) partials [n_parts][3][D] = dgamma | dbeta | dbias for ebn_ff_colsum_finish_f32 (stride = width = 3 * D); in mode 0
+ * the gradient of the broadcast row equals dbias.  partials: ebn_ff_ln_partials_len(R, D) floats.                        */
+int64_t ebn_ff_ln_partials_len(int64_t R, int32_t D);
+int ebn_ff_ln_bwd_f32(const float* dY, const float* xhat, const float* rstd, const float* gamma, int32_t mode, uint32_t drop_key,
+                      float drop_p, float* dX, float* dres, float* partials, int32_t* n_parts, int64_t R, int32_t D,
+                      ebn_stream_t stream);
+/* out[i] = sum_p partials[p * stride + i], i < width: four interleaved chains of ascending p, combined (0 + 1) + (2 + 3).  */
+int ebn_ff_colsum_finish_f32(const float* partials, int64_t n_parts, int64_t stride, int64_t width, float* out,
+                             ebn_stream_t stream);
+/* BertIntermediate after its GEMM: Y = gelu(X + bias), erf form, [R, C]; backward dX = dY * gelu'(X + bias) recomputed from the
+ * saved pre-activation X, dbias [C] its column sum (two launches; partials: ebn_colsum_partials_len(R, C) floats).        */
+int ebn_ff_gelu_fwd_f32(const float* X, const float* bias, float* Y, int64_t R, int32_t C, ebn_stream_t stream);
+int ebn_ff_gelu_bwd_f32(const float* X, const float* bias, const float* dY, float* dX, float* dbias, float* partials, int64_t R,
+                        int32_t C, ebn_stream_t stream);
+/* AttentionPooling (fastformer.py) after att_fc1's GEMM, n_seq sequences of L <= 4096 rows, one workgroup per sequence:
+ *   U [n_seq*L, D] <- tanh(U + b1) in place;  a_l = exp(U_l . w2 + b2[0]) * mask[n, l] (no max-subtraction);
+ *   w_l = a_l / (sum_l a + 1e-8) -> w [n_seq, L];  out [n_seq, D] = sum_l w_l X_l;  sinv [n_seq] = 1 / (sum a + 1e-8).
+ * A sequence whose mask is all zero gets w == 0 and out == 0 exactly.  Not ebn_attpool_fwd_f32 (1e-7, no b2, no mask).     */
+int ebn_ff_pool_fwd_f32(float* U, const float* b1, const float* w2, const float* b2, const float* X, const float* mask, float* out,
+                        float* w, float* sinv, int64_t n_seq, int32_t L, int32_t D, ebn_stream_t stream);
+/* Its backward's direct part from dout [n_seq, D]: dX [n_seq*L, D] = w_l dout (overwritten), de [n_seq*L] = w_l (dw_l - s) with
+ * dw_l = dout . X_l, s = sum_l w_l dw_l, and db2n [n_seq] = the sequence's share of d(b2) = sum_l de_l in its closed form
+ * s * 1e-8 * sinv (the literal sum is pure cancellation).  The rest is ebn_attpool_bwd_dpre_f32 over the rows (q = w2) and GEMMs. */
+int ebn_ff_pool_bwd_f32(const float* X, const float* w, const float* sinv, const float* dout, float* dX, float* de, float* db2n,
+                        int64_t n_seq, int32_t L, int32_t D, ebn_stream_t stream);
+/* Head: score[n] = sigmoid(user[n] . W[0:D] + cand[n] . W[D:2D] + b[0]); backward from dscore [N]: duser, dcand [N, D],
+ * dW [2D] (n ascending), db [1].                                                                                              */
+int ebn_ff_head_fwd_f32(const float* user, const float* cand, const float* W, const float* b, float* score, int64_t N, int32_t D,
+                        ebn_stream_t stream);
+int ebn_ff_head_bwd_f32(const float* user, const float* cand, const float* W, const float* score, const float* dscore, float* duser,
+                        float* dcand, float* dW, float* db, int64_t N, int32_t D, ebn_stream_t stream);
+/* FastSelfAttention between its Linear layers, one workgroup per sequence of T tokens.  Q, K [n_seq*T, D] arrive as x.Wq^T, x.Wk^T
+ * and leave with their biases added (mixed_query_layer / mixed_key_layer, kept for the backward).  hs = D / heads:
+ *   a_h = softmax_t((Q_t . Wqa_h + bqa_h) / sqrt(hs) + (1 - mask_t) * -10000)  -- Wqa [heads, D]: every head reads the WHOLE row;
+ *   pq = per-head sum_t a_h[t] Q_t (on the head's columns);  KP = K * pq;  b_h likewise from KP with Wka, bka;  pk = sum_t b_h[t] KP_t;
+ *   AO [n_seq*T, D] = pk * Q (the input of `transform`);  SV0 (may be NULL) = Q + btr, the buffer transform's GEMM accumulates
+ *   into (beta = 1) for "+ mixed_query_layer".  Saved: qw, kw [n_seq, heads, T], pq, pk [n_seq, D].
+ * Shape rules: D % heads == 0 (else EBN_ERR_BAD_ARG); D % 4 == 0, D <= 1024, heads * D <= 4096, T <= 4096 and
+ * 4 * (T * (D + 4) + 6 * D + heads * T + T) bytes of LDS <= 64 KiB forward, 4 * (T * (D + 4) + 4 * D + 4 * heads * T) backward
+ * (EBN_ERR_UNSUPPORTED); Q, K, AO, SV0 and the weights 16-byte aligned.                                                       */
+int ebn_ff_attn_fwd_f32(float* Q, float* K, const float* bq, const float* bk, const float* btr, const float* Wqa, const float* bqa,
+                        const float* Wka, const float* bka, const float* mask, float* AO, float* SV0, float* qw, float* kw,
+                        float* pq, float* pk, int64_t n_seq, int32_t T, int32_t D, int32_t heads, ebn_stream_t stream);
+/* Its backward from dAO and (may be NULL) dSV, the gradient reaching Q through SV0: dQ, dK [n_seq*T, D] and *n_parts (HOST
+ * out-parameter, <= 256) per-workgroup partials [n_parts][2 * heads * D + 3 * D] = dWqa | dWka | colsum(dQ) | colsum(dK) |
+ * colsum(dSV) (= d(query.bias), d(key.bias), d(transform.bias)) for ebn_ff_colsum_finish_f32.  Workgroup g walks the sequences
+ * g, g + n_parts, ... in ascending order.  The logit biases bqa / bka have identically zero gradients (a softmax does not see a
+ * shift) and are not computed.  partials: ebn_ff_attn_partials_len(n_seq, D, heads) floats.                                  */
+int64_t ebn_ff_attn_partials_len(int64_t n_seq, int32_t D, int32_t heads);
+/* The shape rules above as a pure host query: EBN_OK, or the code ebn_ff_attn_fwd_f32 (and, with_backward != 0, ebn_ff_attn_bwd_f32,
+ * whose LDS bound is the tighter one) would return.  The module asks it before the first launch of a training step.              */
+int ebn_ff_attn_supported(int32_t T, int32_t D, int32_t heads, int32_t with_backward);
+int ebn_ff_attn_bwd_f32(const float* Q, const float* K, const float* Wqa, const float* Wka, const float* qw, const float* kw,
+                        const float* pq, const float* pk, const float* dAO, const float* dSV, float* dQ, float* dK, float* partials,
+                        int32_t* n_parts, int64_t n_seq, int32_t T, int32_t D, int32_t heads, ebn_stream_t stream);
+
 /* Step prologue: copy up to three device buffers (history ids, candidate ids, labels of a batch handed over as device
  * tensors -- the inputs of nrms.py:170-176) into the step's static buffers with ONE launch; n_i in bytes, multiples
  * of 4; a NULL source or n_i = 0 skips that pair.                                                                   */
