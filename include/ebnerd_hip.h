@@ -842,6 +842,45 @@ int ebn_sum_f32(const float* x, int64_t n, float scale, float* out, int32_t accu
 int ebn_sumsq_f32(const float* x, int64_t n, float scale, float* out, int32_t accumulate,
                   ebn_stream_t stream);
 
+/* ---- beyond-accuracy list metrics (paths relative to src/ebrec/evaluation/) ------------------------------------------
+ * Lists are int32 ROW numbers of a device table + int64 CSR offsets [n_lists + 1] into an id array of n_ids entries.  A row
+ * number < 0 or >= n_rows is a MISSING id (get_keys_in_dict, utils.py:155-169): the kernels skip it and never form an address
+ * from it; a list whose offsets leave [0, n_ids] or run backwards is treated as empty.  Any list length is legal, 0 included.
+ * All results are fp32; "undefined" is NaN exactly where the reference returns NaN.  D is any positive width (16-byte loads
+ * when D % 4 == 0 and the table is 16-byte aligned, 4-byte loads otherwise).                                                 */
+/* dst[r] = src[r] / sqrt(sum src[r]^2); a zero row is divided by 1 and stays zero -- sklearn's normalize inside the
+ * cosine_distances the reference passes as pairwise_distance_function (beyond_accuracy.py:3,60).  dst may be src.          */
+int ebn_ba_unit_rows_f32(const float* src, float* dst, int64_t n_rows, int64_t D, ebn_stream_t stream);
+/* IntralistDiversity.__call__ (beyond_accuracy.py:81-96) + intralist_diversity (metrics/_beyond_accuracy.py:45-52) over UNIT
+ * rows: out[l] = sum over positions i != j of clip(1 - u_i . u_j, 0, 2) / (n (n - 1)), n = valid ids of the list (a repeated id
+ * counts once per position); NaN when n < 2.  form 0: lists of at most 10 positions run one wave per list with the rows in
+ * registers, longer ones one workgroup per list over LDS tiles; form 1: every list takes the tiled form (the test hook that
+ * compares the two).                                                                                                         */
+int ebn_ba_intralist_f32(const float* unit, int64_t n_rows, int64_t D, const int32_t* ids, int64_t n_ids, const int64_t* offsets,
+                         int64_t n_lists, int32_t form, float* out, ebn_stream_t stream);
+/* Serendipity.__call__ (beyond_accuracy.py:405-427) + serendipity (metrics/_beyond_accuracy.py:91-94): out[l] = mean over all
+ * n x m pairs (recommendation i of list l, history item j of list l) of clip(1 - u_i . u_j, 0, 2) -- no diagonal is zeroed, the
+ * two sides are different arrays; NaN when either side has no valid id.  form 0: a pair whose shorter side has at most 10
+ * positions runs one wave per pair with that side's rows in registers (D % 4 == 0, D <= 1024, 16-byte aligned table; otherwise,
+ * and for every other pair, one workgroup per pair over LDS tiles); form 1: every pair takes the tiled form.                   */
+int ebn_ba_cross_f32(const float* unit, int64_t n_rows, int64_t D, const int32_t* ids_r, int64_t n_ids_r, const int64_t* off_r,
+                     const int32_t* ids_h, int64_t n_ids_h, const int64_t* off_h, int64_t n_lists, int32_t form, float* out,
+                     ebn_stream_t stream);
+/* The candidates' distance matrix of IntralistDiversity._candidate_diversity (beyond_accuracy.py:130-154), built once:
+ * out [m, m], out[i, j] = clip(1 - u_ids[i] . u_ids[j], 0, 2), exactly 0 where i == j, NaN where either id is missing.
+ * m <= 16 * 65535 (EBN_ERR_UNSUPPORTED beyond).                                                                              */
+int ebn_ba_pairdist_f32(const float* unit, int64_t n_rows, int64_t D, const int32_t* ids, int64_t m, float* out, ebn_stream_t stream);
+/* Sentiment.__call__ (beyond_accuracy.py:295-302; transform 0: mean of values[id]) and Novelty.__call__ + novelty
+ * (beyond_accuracy.py:479-486, metrics/_beyond_accuracy.py:165; transform 1: mean of -log2(values[id])); NaN on a list without a
+ * valid id.                                                                                                                  */
+int ebn_ba_list_mean_f32(const float* values, int64_t n_rows, const int32_t* ids, int64_t n_ids, const int64_t* offsets,
+                         int64_t n_lists, int32_t transform, float* out, ebn_stream_t stream);
+/* The per-combination diversities of _candidate_diversity (beyond_accuracy.py:139-154): subsets [n_subsets, k] int32 indices into
+ * the m x m matrix of ebn_ba_pairdist_f32, out[s] = sum over a != b of dist[s_a, s_b] / (k' (k' - 1)), k' = indices inside
+ * [0, m) (others are skipped); NaN when k' < 2.  Minimum and maximum are taken by the caller.                                 */
+int ebn_ba_subset_sums_f32(const float* dist, int64_t m, const int32_t* subsets, int64_t k, int64_t n_subsets, float* out,
+                           ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
