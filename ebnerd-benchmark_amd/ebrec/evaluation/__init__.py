@@ -2,3 +2,4 @@ from .metrics_protocols import (  # noqa: F401
     AccuracyScore, AucScore, F1Score, LogLossScore, MetricEvaluator, MrrScore, NdcgScore, RootMeanSquaredError,
 )
 from .beyond_accuracy import Coverage, Distribution, IntralistDiversity, Novelty, Serendipity  # noqa: F401
+from .device_metrics import DeviceMetricEvaluator, RaggedLists  # noqa: F401

@@ -56,6 +56,37 @@ def rank_predictions_by_score(arr: Iterable[float]) -> np.ndarray:
     return np.argsort(np.argsort(arr)[::-1]) + 1
 
 
+def rank_predictions_by_score_ragged(scores, offsets_or_lists=None, device="cuda") -> list:
+    """`rank_predictions_by_score` of every list of a ragged batch in one launch of ebn_list_ranks: a list of int64 rank arrays.
+
+    The batch is given as nested lists (or a RaggedLists) in `scores`, as flat `scores` plus `offsets_or_lists` = offsets of
+    n_lists + 1 entries, or -- with ``scores=None`` -- as nested lists in `offsets_or_lists`.  float32 scores are compared as
+    float32, anything else as float64.  A list with tied or non-finite scores is ranked by `rank_predictions_by_score` itself (the
+    order inside a tie group is the host sort's own); so is every list when `device` is None or no GPU is visible."""
+    from ebrec.evaluation.device_metrics import RaggedLists, device_available, device_scores, list_ranks_call
+
+    if scores is None:
+        R = RaggedLists.from_lists(offsets_or_lists, dtype=None)
+    elif offsets_or_lists is None:
+        R = RaggedLists.from_lists(scores)
+    else:
+        R = RaggedLists(scores, offsets_or_lists)
+    off = R.offsets.tolist()
+    if not device_available(device) or len(R) == 0:
+        flat = R.host_flat()
+        return [rank_predictions_by_score(flat[a:b]) for a, b in zip(off[:-1], off[1:])]
+    import torch
+
+    dev_scores, _ = device_scores(R.flat, device)
+    ranks, flags = list_ranks_call(dev_scores, torch.from_numpy(R.offsets).to(dev_scores.device))
+    out = np.split(ranks.astype(np.int64), R.offsets[1:-1])
+    if flags.any():
+        flat = R.host_flat()
+        for l in np.flatnonzero(flags).tolist():
+            out[l] = rank_predictions_by_score(flat[off[l]:off[l + 1]])
+    return out
+
+
 def write_submission_file(impression_ids: Iterable[int], prediction_scores: Iterable, path=Path("predictions.txt"),
                           rm_file: bool = True, filename_zip: str = None) -> None:
     """One ``<impression_id> [r1,r2,...]`` line per impression, then zipped (reference _python.py:62-90)."""

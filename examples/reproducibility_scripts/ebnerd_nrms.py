@@ -29,7 +29,7 @@ sys.path.insert(0, str(ROOT / "ebnerd-benchmark_amd"))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from args_nrms import get_args  # noqa: E402
-from ebrec.evaluation import AucScore, MetricEvaluator, MrrScore, NdcgScore  # noqa: E402
+from ebrec.evaluation import AucScore, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore  # noqa: E402
 from ebrec.models.newsrec import NRMSModel  # noqa: E402
 from ebrec.models.newsrec.callbacks import EarlyStopping, ModelCheckpoint, ReduceLROnPlateau, TensorBoard  # noqa: E402
 from ebrec.models.newsrec.dataloader import NRMSDataLoader, NRMSDataLoaderPretransform  # noqa: E402
@@ -42,7 +42,8 @@ from ebrec.utils._constants import (DEFAULT_BODY_COL, DEFAULT_CLICKED_ARTICLES_C
                                     DEFAULT_IS_BEYOND_ACCURACY_COL, DEFAULT_LABELS_COL, DEFAULT_SUBTITLE_COL, DEFAULT_TITLE_COL,
                                     DEFAULT_USER_COL)
 from ebrec.utils._frames import concat_str_columns, split_df_chunks, with_column  # noqa: E402
-from ebrec.utils._python import rank_predictions_by_score, write_json_file, write_submission_file  # noqa: E402
+from ebrec.utils._python import (rank_predictions_by_score, rank_predictions_by_score_ragged, write_json_file,  # noqa: E402
+                                 write_submission_file)
 
 
 def hash_tokenize(texts, max_length: int, vocab_size: int):
@@ -177,8 +178,9 @@ def run(args, hparams, build_model, article_mapping, MODEL_NAME, after_validatio
         parts = [None] * world
         torch.distributed.all_gather_object(parts, ([list(l) for l in labels], [list(x) for x in scores]))
         labels, scores = [l for p in parts for l in p[0]], [x for p in parts for x in p[1]]
-    metrics = MetricEvaluator(labels=labels, predictions=scores,
-                              metric_functions=[AucScore(), MrrScore(), NdcgScore(k=5), NdcgScore(k=10)]).evaluate()
+    Evaluator = DeviceMetricEvaluator if getattr(args, "device_metrics", False) else MetricEvaluator
+    metrics = Evaluator(labels=labels, predictions=scores,
+                        metric_functions=[AucScore(), MrrScore(), NdcgScore(k=5), NdcgScore(k=10)]).evaluate()
     if rank == 0:
         print(metrics)
         write_json_file(metrics.evaluations, ARTIFACT_DIR / "validation_metrics.json")
@@ -207,8 +209,14 @@ def run(args, hparams, build_model, article_mapping, MODEL_NAME, after_validatio
     def predict_frame(frame, bs):
         scores = model.scorer.predict(mk(frame, True, bs))
         frame = add_prediction_scores(frame, scores.tolist())
-        return with_column(frame, "ranked_scores", [list(rank_predictions_by_score(x)) for x in frame["scores"]])
+        if getattr(args, "device_metrics", False):
+            ranked = [list(r) for r in rank_predictions_by_score_ragged(frame["scores"].tolist())]
+        else:
+            ranked = [list(rank_predictions_by_score(x)) for x in frame["scores"]]
+        return with_column(frame, "ranked_scores", ranked)
 
+    # with --device_metrics the scores stay next to their ranks in test_predictions.parquet, so that the ranking can be checked
+    OUT_COLUMNS = [DEFAULT_IMPRESSION_ID_COL, "ranked_scores"] + (["scores"] if getattr(args, "device_metrics", False) else [])
     # --chunks_done N resumes a crashed run: finished chunks are re-read from <dump_dir>/resume (the reference
     # keeps them under its time-stamped artefact directory, where a restarted run cannot find them)
     RESUME_DIR = Path(args.dump_dir) / "resume"
@@ -220,14 +228,14 @@ def run(args, hparams, build_model, article_mapping, MODEL_NAME, after_validatio
     done = [pd.read_parquet(RESUME_DIR / f"pred_wo_ba_{i}.parquet") for i in range(1, args.chunks_done + 1)]
     for i, chunk in enumerate(chunks[args.chunks_done:], start=1 + args.chunks_done):
         print(f"Test chunk: {i}/{len(chunks)}")
-        chunk = predict_frame(chunk, args.batch_size_test_wo_b)[[DEFAULT_IMPRESSION_ID_COL, "ranked_scores"]]
+        chunk = predict_frame(chunk, args.batch_size_test_wo_b)[OUT_COLUMNS]
         if writer:
             chunk.to_parquet(TEST_CHUNKS_DIR / f"pred_wo_ba_{i}.parquet")
             chunk.to_parquet(RESUME_DIR / f"pred_wo_ba_{i}.parquet")
         done.append(chunk)
         gc.collect()
     print("Initiating testset with beyond-accuracy...")
-    pred_w = predict_frame(df_w, args.batch_size_test_w_b)[[DEFAULT_IMPRESSION_ID_COL, "ranked_scores"]] if len(df_w) else None
+    pred_w = predict_frame(df_w, args.batch_size_test_w_b)[OUT_COLUMNS] if len(df_w) else None
     if not writer:
         return hist, metrics.evaluations
     df_out = pd.concat(done + ([pred_w] if pred_w is not None else []), ignore_index=True)

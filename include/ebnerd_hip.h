@@ -881,6 +881,48 @@ int ebn_ba_list_mean_f32(const float* values, int64_t n_rows, const int32_t* ids
 int ebn_ba_subset_sums_f32(const float* dist, int64_t m, const int32_t* subsets, int64_t k, int64_t n_subsets, float* out,
                            ebn_stream_t stream);
 
+/* ---- per-impression ranking metrics over ragged lists (paths relative to src/ebrec/) ----------------------------------------
+ * Lists are a flat score array (score_kind EBN_RM_F32 or EBN_RM_F64; scores are COMPARED in that type, unrounded), a flat uint8
+ * label array (0 / non-zero) and int64 CSR offsets [n_lists + 1] into both (n_items entries each, n_items <= 2^31 - 257).  A list
+ * whose offsets leave [0, n_items] or run backwards is treated as empty; any length is legal, 0 and 1 included.  A candidate's rank
+ * comes from counting, rank_i = 1 + #{j : s_j > s_i} + #{j < i : s_j == s_i}; everything after the comparisons is fp64.
+ * Per-list flag byte: bit 0 "tie-ambiguous" = two EQUAL scores of the list carry DIFFERENT labels (the only case in which
+ * mrr / ndcg depend on the order inside a tie group, which on the host is the order of an unstable argsort); bit 1 = the list
+ * holds a non-finite score.  The caller recomputes flagged lists on the host.
+ * form 0: a list of at most 16 candidates runs in a 16-lane group (four lists per wave), one of at most 64 in one wave, a longer one
+ * with a whole workgroup over an LDS copy of the list (at most 1024 candidates) or over 1024-candidate tiles re-read from global
+ * memory; form 1: every list takes the last, general form (the test hook that compares the forms).                              */
+#define EBN_RM_MAX_SLOTS 16
+#define EBN_RM_F32 0
+#define EBN_RM_F64 1
+#define EBN_RM_AUC 0      /* roc_auc_score (metrics/_sklearn.py): (#{pos > neg} + #{pos == neg} / 2) / (n_pos n_neg)                 */
+#define EBN_RM_MRR 1      /* mrr_score (metrics/_ranking.py:152-155): sum y_i / rank_i / n_pos                                        */
+#define EBN_RM_NDCG 2     /* ndcg_score (:121-123), param = k: gains 2^y - 1, discounts log2(rank + 1), ranks <= min(k, n)            */
+#define EBN_RM_LOGLOSS 3  /* LogLossScore (metrics_protocols.py:99): scores clipped to [10e-12, 1 - 10e-12]                           */
+#define EBN_RM_RMSE 4     /* sqrt(mean (y - s)^2)                                                                                     */
+#define EBN_RM_ACCURACY 5 /* param = threshold: mean((s >= threshold) == y)                                                           */
+#define EBN_RM_F1 6       /* param = threshold: 2 tp / (2 tp + fp + fn) of s >= threshold, 0.0 on a zero denominator                  */
+/* Bytes of the workspace ebn_rank_metrics needs for n_lists lists (one partial per slot and workgroup; 0 for n_lists outside
+ * [0, 2^31 - 1]).                                                                                                              */
+int64_t ebn_rank_metrics_workspace_bytes(int64_t n_lists);
+/* MetricEvaluator.evaluate (evaluation/metrics_protocols.py:141-217) for up to EBN_RM_MAX_SLOTS metrics in one pass.  slot_kind /
+ * slot_param are DEVICE arrays of n_slots entries (an unknown kind gives NaN).  Outputs, all on the device:
+ *   sums [n_slots] fp64: the sum of the slot's per-list values over the lists that are left to the device -- a list with flag bit 1
+ *     adds to no sum, one with bit 0 to no mrr / ndcg sum, a one-class list to no auc / logloss sum (there the host raises); any
+ *     other NaN value (mrr / ndcg of a list without a positive, rmse / accuracy of an empty list) is added, as np.mean would;
+ *   flags [n_lists]; counters [3] = lists with one class only (empty ones included), with bit 0, with bit 1;
+ *   per_list (may be NULL) [n_slots, n_lists] fp64: every list's value, NaN where the host functions give NaN or raise.
+ * Sums are taken in a fixed order (lane tree, one running sum per lane group, 16 per workgroup, a closing launch over the
+ * workgroups): no floating-point atomics, two runs give the same bits.  workspace: 16-byte aligned device memory.               */
+int ebn_rank_metrics(const void* scores, int32_t score_kind, const uint8_t* labels, int64_t n_items, const int64_t* offsets,
+                     int64_t n_lists, const int32_t* slot_kind, const double* slot_param, int32_t n_slots, int32_t form, double* sums,
+                     uint8_t* flags, int64_t* counters, double* per_list, void* workspace, int64_t workspace_bytes,
+                     ebn_stream_t stream);
+/* rank_predictions_by_score (utils/_python.py:41-59) of every list: ranks [n_items] int32, 1 for the highest score.  A list with
+ * ANY two equal scores (flag bit 0) or a non-finite score (bit 1) is left to the host: its ranks are written as 0.               */
+int ebn_list_ranks(const void* scores, int32_t score_kind, int64_t n_items, const int64_t* offsets, int64_t n_lists, int32_t form,
+                   int32_t* ranks, uint8_t* flags, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
