@@ -192,6 +192,21 @@ __device__ __forceinline__ void gru_tile_gemm(const GruArgs& a, const float* __r
   }
 }
 
+// gate epilogue of unit u of one live step: gx = the sequence's row of X.W_k, acc = h.U_rec of the three gate columns; returns h'.
+// Contraction is off: the training and the inference step kernel must round alike (the inference result is tested bit for bit
+// against the training kernel's), and left to itself the compiler fuses r * gh_h into the add in one of them only.
+__device__ __forceinline__ float gru_gates(const float* __restrict__ gx, const float* __restrict__ bias, int64_t U, int u, float h,
+                                           const float* acc, float& z, float& r, float& n, float& ghh) {
+#pragma clang fp contract(off)
+  const float* bi = bias;
+  const float* br = bias + 3 * U;
+  z = sigmoidf(gx[u] + bi[u] + (acc[0] + br[u]));
+  r = sigmoidf(gx[U + u] + bi[U + u] + (acc[1] + br[U + u]));
+  ghh = acc[2] + br[2 * U + u];
+  n = tanhf(gx[2 * U + u] + bi[2 * U + u] + r * ghh);
+  return z * h + (1.f - z) * n;
+}
+
 __global__ __launch_bounds__(GRU_THREADS) void gru_fwd_step_kernel(GruArgs a) {
   __shared__ int live[GRU_BM];
   const int tid = threadIdx.x, tx = tid % GRU_BU, ty = tid / GRU_BU;
@@ -211,22 +226,49 @@ __global__ __launch_bounds__(GRU_THREADS) void gru_fwd_step_kernel(GruArgs a) {
   const float h = hprev != nullptr ? hprev[b * U + u] : 0.f;
   if (t == 0) a.Hs[b * U + u] = h;
   float z = 0.f, r = 0.f, n = 0.f, ghh = 0.f, hn = h;
-  if (live[ty]) {
-    const float* gx = a.gx + (b * a.H + t) * 3 * U;
-    const float* bi = a.bias;
-    const float* br = a.bias + 3 * U;
-    z = sigmoidf(gx[u] + bi[u] + (acc[0] + br[u]));
-    r = sigmoidf(gx[U + u] + bi[U + u] + (acc[1] + br[U + u]));
-    ghh = acc[2] + br[2 * U + u];
-    n = tanhf(gx[2 * U + u] + bi[2 * U + u] + r * ghh);
-    hn = z * h + (1.f - z) * n;
-  }
+  if (live[ty]) hn = gru_gates(a.gx + (b * a.H + t) * 3 * U, a.bias, U, u, h, acc, z, r, n, ghh);
   a.Hs[(static_cast<int64_t>(t) + 1) * B * U + b * U + u] = hn;
   float* ac = a.act + (static_cast<int64_t>(t) * B + b) * 4 * U;
   ac[u] = z;
   ac[U + u] = r;
   ac[2 * U + u] = n;
   ac[3 * U + u] = ghh;
+}
+
+// Inference step t over a once-encoded catalogue (scorer.predict from cached news vectors): the same tile GEMM and gate epilogue,
+// but the sequence's gx row is GX_all[his_idx[b, t]] (GX_all = news_all.W_k, one GEMM per predict), the step mask is the per-article
+// flag live_all[row] (= any(news_all[row] != 0), the predicate of step_mask, built with the cache) and h moves between two
+// (B, U) buffers: nothing is kept for a backward pass.  A row number outside [0, n_rows) sets *oob and masks the step.
+__global__ __launch_bounds__(GRU_THREADS) void gru_infer_step_kernel(GruArgs a, const float* __restrict__ gx_all,
+                                                                     const int32_t* __restrict__ live_all, int64_t n_rows,
+                                                                     const int32_t* __restrict__ his_idx, const float* hin,
+                                                                     float* __restrict__ hout, int32_t* __restrict__ oob) {
+  __shared__ int row[GRU_BM];  // catalogue row of the sequence's step, -1: masked
+  const int tid = threadIdx.x, tx = tid % GRU_BU, ty = tid / GRU_BU;
+  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * GRU_BM;
+  const int u0 = static_cast<int>(blockIdx.y) * GRU_BU;
+  const int64_t B = a.B, U = a.U;
+  if (tid < GRU_BM) {
+    int r = -1;
+    if (b0 + tid < B) {
+      const int32_t i = his_idx[(b0 + tid) * a.H + a.t];
+      if (i >= 0 && static_cast<int64_t>(i) < n_rows) {
+        if (live_all[i] != 0) r = i;
+      } else if (oob != nullptr) {
+        *oob = 1;
+      }
+    }
+    row[tid] = r;
+  }
+  float acc[3] = {0.f, 0.f, 0.f};
+  gru_tile_gemm<0>(a, hin, b0, u0, acc);  // its barriers also publish row[]
+  const int64_t b = b0 + ty;
+  const int u = u0 + tx;
+  if (b >= B || u >= U) return;
+  const float h = hin != nullptr ? hin[b * U + u] : 0.f;
+  float z, r, n, ghh, hn = h;
+  if (row[ty] >= 0) hn = gru_gates(gx_all + static_cast<int64_t>(row[ty]) * 3 * U, a.bias, U, u, h, acc, z, r, n, ghh);
+  hout[b * U + u] = hn;
 }
 
 __global__ __launch_bounds__(GRU_THREADS) void gru_bwd_step_kernel(GruArgs a) {
@@ -361,6 +403,31 @@ extern "C" int ebn_gru_bwd_f32(const float* dhH, const float* X, const float* Wr
   for (int32_t t = H; t >= 0; --t) {
     a.t = t;
     EBN_LAUNCH(gru_bwd_step_kernel, grid, dim3(GRU_THREADS), 0, ebn_stream(stream), a);
+    EBN_CHECK_LAUNCH();
+  }
+  return EBN_OK;
+}
+
+extern "C" int ebn_gru_infer_indexed_f32(const float* gx_all, const int32_t* live_all, int64_t n_rows, const int32_t* his_idx,
+                                         const float* Wrec, const float* bias, const float* h0, float* h_work, float* h_out, int64_t B,
+                                         int32_t H, int32_t U, int32_t* oob_flag, ebn_stream_t stream) {
+  EBN_REQUIRE(his_idx && Wrec && bias && h_work && h_out && n_rows >= 0 && (n_rows == 0 || (gx_all && live_all)), EBN_ERR_BAD_ARG);
+  const int rc = gru_check(B, H, U, U);
+  if (rc != EBN_OK) return rc;
+  EBN_REQUIRE(n_rows <= EBN_DIM_MAX, EBN_ERR_UNSUPPORTED);
+  EBN_REQUIRE(ebn_aligned16(Wrec) && ebn_aligned16(h0) && ebn_aligned16(h_work) && ebn_aligned16(h_out), EBN_ERR_ALIGN);
+  EBN_REQUIRE(h_work != h_out && h0 != h_work && h0 != h_out, EBN_ERR_BAD_ARG);  // a step reads one buffer and writes the other
+  if (B == 0) return EBN_OK;
+  GruArgs a = gru_args(B, H, U, U);
+  a.Wrec = Wrec;
+  a.bias = bias;
+  const dim3 grid = gru_grid(B, U);
+  for (int32_t t = 0; t < H; ++t) {
+    a.t = t;
+    float* hout = (H - 1 - t) % 2 == 0 ? h_out : h_work;  // the last step writes h_out
+    const float* hin = t == 0 ? h0 : ((H - t) % 2 == 0 ? h_out : h_work);
+    EBN_LAUNCH(gru_infer_step_kernel, grid, dim3(GRU_THREADS), 0, ebn_stream(stream), a, gx_all, live_all, n_rows, his_idx, hin, hout,
+               oob_flag);
     EBN_CHECK_LAUNCH();
   }
   return EBN_OK;

@@ -6,7 +6,8 @@ Per impression b with user index u_b (lstur.py:56-201):
   user:   long_b = user_emb[u_b];  GRU over the H history news vectors (steps with an all-zero vector are skipped: Masking(0.0))
           type "ini": h0 = long_b, user = h_H;  type "con": h0 = 0, user = [h_H, long_b].Wd + bd
   scores = cand . user -> softmax + compiled loss (training), sigmoid (scorer)
-The news encoder does not depend on the user; candidates are still encoded per batch (no article cache in the scorer).
+The news encoder does not depend on the user: scorer.predict over an eval loader encodes the loader's article matrix once
+(encode_catalogue) and runs each batch from the cached news vectors, GRU input projections and step masks (score_cached).
 
 Data layout in HBM (fp32 row-major):
   table        (V, E)              word embeddings (trainable: fixed-point gradient accumulator + fused Adam sweep)
@@ -19,6 +20,7 @@ Data layout in HBM (fp32 row-major):
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -106,6 +108,7 @@ class LSTUREngine:
         self.oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.user_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.row_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)  # a history row outside an encoded catalogue
         self.loss_dev = torch.zeros(1, device=dev)
         st = _hip.StepState()
         st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
@@ -208,11 +211,16 @@ class LSTUREngine:
     # ------------------------------------------------------------------ kernels
     def _encode(self, b: _Bufs, train: bool, expand=None):
         """Forward of every title and user of the buffers' batch (ids / uidx already staged); training: dropout on."""
+        self._encode_news(b, train, expand)
+        self._encode_users(b)
+
+    def _encode_news(self, b: _Bufs, train: bool, expand=None, users: bool = True):
+        """The title encoder over the buffers' N titles -> b.NV; users: also the gather of the batch's user-table rows -> b.Eu."""
         S = _hip.stream_handle
         call, pt = _hip.call, _hip.ptr
         P = self.params
         st = pt(self.state) if train else None
-        B, N, R, T, E, F, A, U, H = b.B, b.N, b.R, self.T, self.E, self.F, self.A, self.U, self.H
+        B, N, R, T, E, F, A, U = b.B, b.N, b.R, self.T, self.E, self.F, self.A, self.U
         f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
         p_in = self.p if train else 0.0
         if expand is not None:  # article-row numbers -> token ids on the device (dataloader.py:169-179)
@@ -220,24 +228,41 @@ class LSTUREngine:
                  pt(self.oob_flag), S())
         call("ebn_gather_rows_f32", pt(b.ids), pt(self.table), pt(b.X), R, E, self.V, st, SITE_NEWS_IN if p_in > 0 else -1,
              ctypes.c_float(p_in), pt(self.oob_flag), S())
-        call("ebn_gather_rows_f32", pt(b.uidx), pt(self.user_table), pt(b.Eu), B, U, self.n_users + 1, None, -1, f0,
-             pt(self.user_oob_flag), S())
+        if users:
+            call("ebn_gather_rows_f32", pt(b.uidx), pt(self.user_table), pt(b.Eu), B, U, self.n_users + 1, None, -1, f0,
+                 pt(self.user_oob_flag), S())
         Wb = P.view("conv_Wb")
         call("ebn_conv1d_fwd_f32", pt(b.X), pt(Wb), pt(Wb[self.window * E]), pt(b.Vd), N, T, E, F, self.window, st,
              SITE_CONV if p_in > 0 else -1, ctypes.c_float(p_in), -1, f0, S())
         call("ebn_gemm_f32", 0, 0, R, A, F, f1, pt(b.Vd), F, pt(P.view("att_W")), A, f0, pt(b.Ua), A, S())
         call("ebn_attpool_masked_fwd_f32", pt(b.Ua), pt(P.view("att_b")), pt(P.view("att_q")), pt(b.Vd), pt(b.ids), pt(b.NV),
              pt(b.w), N, T, F, A, S())
+
+    def _encode_users(self, b: _Bufs):
+        """The user encoder over the first B*H news vectors of b.NV (b.Eu gathered): GRU, and for "con" the Dense."""
+        S = _hip.stream_handle
+        call, pt = _hip.call, _hip.ptr
+        P = self.params
+        B, F, U, H = b.B, self.F, self.U, self.H
+        f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
         his = b.NV[: B * H]
         call("ebn_gemm_f32", 0, 0, B * H, 3 * U, F, f1, pt(his), F, pt(P.view("gru_k")), 3 * U, f0, pt(b.gx), 3 * U, S())
         h0 = pt(b.Eu) if self.type == "ini" else None
         call("ebn_gru_fwd_f32", pt(b.gx), pt(his), pt(P.view("gru_r")), pt(P.view("gru_b")), h0, pt(b.Hs), pt(b.act), B, H, F, U,
              S())
-        if self.type == "con":  # Dense(U)(concat[h_H, long_u]) = 1.bd + h_H.Wd[:U] + long_u.Wd[U:]
-            Wd = P.view("dense_W")
-            call("ebn_gemm_f32", 0, 0, B, U, 1, f1, pt(b.ones), 1, pt(P.view("dense_b")), U, f0, pt(b.user), U, S())
-            call("ebn_gemm_f32", 0, 0, B, U, U, f1, pt(b.Hs[H]), U, pt(Wd[:U]), U, f1, pt(b.user), U, S())
-            call("ebn_gemm_f32", 0, 0, B, U, U, f1, pt(b.Eu), U, pt(Wd[U:]), U, f1, pt(b.user), U, S())
+        if self.type == "con":
+            self._con_dense(b.Hs[H], b.Eu, b.user, b.ones, B)
+
+    def _con_dense(self, hH, Eu, user, ones, B):
+        """type "con": Dense(U)(concat[h_H, long_u]) = 1.bd + h_H.Wd[:U] + long_u.Wd[U:]"""
+        S = _hip.stream_handle
+        call, pt = _hip.call, _hip.ptr
+        P, U = self.params, self.U
+        f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
+        Wd = P.view("dense_W")
+        call("ebn_gemm_f32", 0, 0, B, U, 1, f1, pt(ones), 1, pt(P.view("dense_b")), U, f0, pt(user), U, S())
+        call("ebn_gemm_f32", 0, 0, B, U, U, f1, pt(hH), U, pt(Wd[:U]), U, f1, pt(user), U, S())
+        call("ebn_gemm_f32", 0, 0, B, U, U, f1, pt(Eu), U, pt(Wd[U:]), U, f1, pt(user), U, S())
 
     def _user_vec(self, b: _Bufs):
         return b.Hs[self.H] if self.type == "ini" else b.user
@@ -395,13 +420,77 @@ class LSTUREngine:
                   1 if sigmoid else 0, _hip.stream_handle())
         return out
 
+    # ------------------------------------------------------------------ scoring from a once-encoded catalogue
+    def encode_catalogue(self, tokens, chunk=8192):
+        """Everything scorer.predict needs of the articles alone, for the CURRENT weights (build it per predict, never keep it on the
+        model): tokens (n_rows, T) -> cache with news_all (n_rows, F), gx_all = news_all . gru_k (n_rows, 3U) -- the GRU's input
+        projection is per article -- and live (n_rows,) int32 = any(news_all != 0), the GRU's Masking(0.0) step mask.  Encoded in
+        chunks: the scratch is that of `chunk` titles whatever n_rows is."""
+        tokens = np.asarray(tokens)
+        if tokens.ndim != 2 or tokens.shape[1] != self.T:
+            raise ValueError(f"catalogue tokens must be (n_rows, {self.T}), got {tuple(tokens.shape)}")
+        self._host_ranges(np.zeros(0, np.int64), tokens)
+        n_rows = tokens.shape[0]
+        F, U = self.F, self.U
+        news_all = torch.empty(n_rows, F, device=self.device)
+        b = _Bufs(self, 0, min(chunk, n_rows), train=False) if n_rows else None
+        for s in range(0, n_rows, chunk):
+            n = min(chunk, n_rows - s)
+            if n != b.N:
+                b = _Bufs(self, 0, n, train=False)  # the short last chunk
+            self._put(b.ids, tokens[s:s + n])
+            self._encode_news(b, False, users=False)
+            news_all[s:s + n].copy_(b.NV)
+        gx_all = torch.empty(n_rows, 3 * U, device=self.device)
+        if n_rows:
+            _hip.call("ebn_gemm_f32", 0, 0, n_rows, 3 * U, F, ctypes.c_float(1.0), _hip.ptr(news_all), F, _hip.ptr(self.params.view("gru_k")),
+                      3 * U, ctypes.c_float(0.0), _hip.ptr(gx_all), 3 * U, _hip.stream_handle())
+        live = (news_all != 0).any(dim=1).to(torch.int32).contiguous()
+        self._check_oob()
+        return SimpleNamespace(news_all=news_all, gx_all=gx_all, live=live, n_rows=n_rows)
+
+    def score_cached(self, cache, user, his_idx, cand_idx, cand_imp, sigmoid=True):
+        """act(news_all[cand_i] . user[cand_imp[i]]) of one indexed batch: user (b,) user indexes, his_idx (b, H) / cand_idx (n,) rows
+        of the cache, cand_imp (n,) the impression of each candidate.  User-table gather -> indexed GRU over the cached input
+        projections -> ("con") Dense -> ragged pair dot against the cached news vectors."""
+        user = self._uidx(user)
+        his_idx, cand_idx = np.asarray(his_idx), np.asarray(cand_idx).reshape(-1)
+        if his_idx.ndim != 2 or user.shape[0] != his_idx.shape[0]:
+            raise ValueError(f"indexed batches need user (b,) and his_idx (b, H), got {tuple(user.shape)} {tuple(his_idx.shape)}")
+        self._host_ranges(user)
+        if cand_idx.size and (cand_idx.min() < 0 or cand_idx.max() >= cache.n_rows):
+            raise IndexError(f"article row out of range [0, {cache.n_rows}) for the encoded catalogue")
+        S = _hip.stream_handle
+        call, pt = _hip.call, _hip.ptr
+        B, H, n, U = his_idx.shape[0], his_idx.shape[1], cand_idx.shape[0], self.U
+        dev = self.device
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        uidx, hi, ci, ui = i32(user), i32(his_idx.reshape(-1)), i32(cand_idx), i32(np.asarray(cand_imp).reshape(-1))
+        Eu, h_work, h_out = (torch.empty(B, U, device=dev) for _ in range(3))
+        call("ebn_gather_rows_f32", pt(uidx), pt(self.user_table), pt(Eu), B, U, self.n_users + 1, None, -1, ctypes.c_float(0.0),
+             pt(self.user_oob_flag), S())
+        call("ebn_gru_infer_indexed_f32", pt(cache.gx_all), pt(cache.live), cache.n_rows, pt(hi), pt(self.params.view("gru_r")),
+             pt(self.params.view("gru_b")), pt(Eu) if self.type == "ini" else None, pt(h_work), pt(h_out), B, H, U,
+             pt(self.row_oob_flag), S())
+        user_vec = h_out
+        if self.type == "con":
+            user_vec = torch.empty(B, U, device=dev)
+            self._con_dense(h_out, Eu, user_vec, torch.ones(max(B, 1), device=dev), B)
+        out = torch.empty(n, device=dev)
+        call("ebn_pair_score_f32", pt(user_vec), pt(cache.news_all), pt(ui), pt(ci), pt(out), n, self.F, 1 if sigmoid else 0, S())
+        self._check_oob()
+        return out
+
     def _check_oob(self):
-        flags = torch.cat([self.oob_flag, self.user_oob_flag, self.range_flag])
-        oob, uoob, rng_bad = (int(v) for v in flags.cpu().tolist())
-        if oob or uoob or rng_bad:
+        flags = torch.cat([self.oob_flag, self.user_oob_flag, self.range_flag, self.row_oob_flag])
+        oob, uoob, rng_bad, row_bad = (int(v) for v in flags.cpu().tolist())
+        if oob or uoob or rng_bad or row_bad:
             self.oob_flag.zero_()
             self.user_oob_flag.zero_()
             self.range_flag.zero_()
+            self.row_oob_flag.zero_()
+        if row_bad:
+            raise IndexError("article row out of range for the encoded catalogue")
         if uoob:
             raise IndexError(f"user index out of range [0, {self.n_users}] for the user embedding table")
         if oob:

@@ -7,7 +7,9 @@ Per article (naml.py _build_newsencoder):
   news    = AttLayer2 over the 4 views [title, body, vert, subvert]
 Per impression: user = AttLayer2 over the H history news vectors (encoded with dropout in training);
   train: softmax(cand . user) + compiled loss;  scorer: sigmoid(cand_one . user).
-The news encoder does not depend on the user; candidates are still encoded per batch (no article cache in the scorer).
+The news encoder does not depend on the user, and neither does the user encoder's logit of a history item (an unmasked
+AttLayer2: a = exp(tanh(x.W + b).q) per article): scorer.predict over an eval loader encodes the loader's article catalogue
+once (encode_catalogue) and scores each batch with one indexed pooling-and-scoring launch (score_cached).
 
 Data layout in HBM (fp32 row-major):
   table      (V, E)           word embeddings (trainable: fixed-point gradient accumulator + fused Adam sweep)
@@ -20,6 +22,7 @@ Data layout in HBM (fp32 row-major):
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -115,6 +118,7 @@ class NAMLEngine:
         self.oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.cat_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.row_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)  # a row number outside an encoded catalogue
         self.loss_dev = torch.zeros(1, device=dev)
         st = _hip.StepState()
         st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
@@ -211,11 +215,24 @@ class NAMLEngine:
     def _encode(self, b: _Bufs, train: bool, user: bool = True):
         """Forward of every article of the buffers' batch (ids already staged); training: dropout on.  user: also the user
         pooling (inference; a training step runs it inside the fused head)."""
+        self._encode_news(b, train)
+        S = _hip.stream_handle
+        call, pt = _hip.call, _hip.ptr
+        P = self.params
+        B, F, A, H = b.B, self.F, self.A, self.H
+        f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
+        his = b.NV[: B * H]
+        call("ebn_gemm_f32", 0, 0, B * H, A, F, f1, pt(his), F, pt(P.view("u_W")), A, f0, pt(b.Uu), A, S())
+        if user:
+            call("ebn_attpool_fwd_f32", pt(b.Uu), pt(P.view("u_b")), pt(P.view("u_q")), pt(his), pt(b.user), pt(b.wu), B, H, F, A, S())
+
+    def _encode_news(self, b: _Bufs, train: bool):
+        """The news encoder over the buffers' N articles (four views, view attention) -> b.NV."""
         S = _hip.stream_handle
         call, pt = _hip.call, _hip.ptr
         P = self.params
         st = pt(self.state) if train else None
-        B, N, E, F, A, H, W = b.B, b.N, self.E, self.F, self.A, self.H, self.window
+        N, E, F, A, W = b.N, self.E, self.F, self.A, self.window
         f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
         p = self.p if train else 0.0
         on = p > 0
@@ -235,10 +252,6 @@ class NAMLEngine:
         call("ebn_gemm_f32", 0, 0, N_VIEWS * N, A, F, f1, pt(b.Vw), F, pt(P.view("va_W")), A, f0, pt(b.Uv), A, S())
         call("ebn_naml_viewatt_fwd_f32", pt(b.Uv), pt(P.view("va_b")), pt(P.view("va_q")), pt(b.Vw), pt(b.wv), pt(b.NV), N, N_VIEWS,
              F, A, S())
-        his = b.NV[: B * H]
-        call("ebn_gemm_f32", 0, 0, B * H, A, F, f1, pt(his), F, pt(P.view("u_W")), A, f0, pt(b.Uu), A, S())
-        if user:
-            call("ebn_attpool_fwd_f32", pt(b.Uu), pt(P.view("u_b")), pt(P.view("u_q")), pt(his), pt(b.user), pt(b.wu), B, H, F, A, S())
 
     def _train_kernels(self, b: _Bufs, C: int):
         """One optimizer step on the staged batch: step advance, forward, loss, backward, Adam (dense buffer, word table)."""
@@ -405,13 +418,69 @@ class NAMLEngine:
                   1 if sigmoid else 0, _hip.stream_handle())
         return out
 
+    # ------------------------------------------------------------------ scoring from a once-encoded catalogue
+    def encode_catalogue(self, title, body, vert, subvert, chunk=4096):
+        """Everything scorer.predict needs of the articles alone, for the CURRENT weights (build it per predict, never keep it on the
+        model): four aligned arrays -- title tokens (n_rows, T), body tokens (n_rows, Tb), vert (n_rows,), subvert (n_rows,) -> cache
+        with news_all (n_rows, F) and a_all (n_rows,) = exp(tanh(news_all.Wu + bu).qu), the user AttLayer2's logit of each article.
+        Encoded in chunks: the scratch is that of `chunk` articles whatever n_rows is."""
+        n_rows = int(np.shape(title)[0])
+        if n_rows == 0:
+            return SimpleNamespace(news_all=torch.empty(0, self.F, device=self.device), a_all=torch.empty(0, device=self.device), n_rows=0)
+        t, bo, v, s_ = self._arrays((np.asarray(title).reshape(n_rows, 1, -1), np.asarray(body).reshape(n_rows, 1, -1),
+                                     np.asarray(vert).reshape(n_rows, 1, 1), np.asarray(subvert).reshape(n_rows, 1, 1)), "catalogue")
+        S = _hip.stream_handle
+        call, pt = _hip.call, _hip.ptr
+        F, A, P = self.F, self.A, self.params
+        f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
+        news_all, a_all = torch.empty(n_rows, F, device=self.device), torch.empty(n_rows, device=self.device)
+        b = _Bufs(self, 0, min(chunk, n_rows), train=False)
+        for s in range(0, n_rows, chunk):
+            n = min(chunk, n_rows - s)
+            if n != b.N:
+                b = _Bufs(self, 0, n, train=False)  # the short last chunk
+            for dst, src in ((b.ids_t, t), (b.ids_b, bo), (b.cat_v, v), (b.cat_s, s_)):
+                self._put(dst, src[s:s + n])
+            self._encode_news(b, False)
+            news_all[s:s + n].copy_(b.NV)
+        Uu = torch.empty(n_rows, A, device=self.device)
+        call("ebn_gemm_f32", 0, 0, n_rows, A, F, f1, pt(news_all), F, pt(P.view("u_W")), A, f0, pt(Uu), A, S())
+        call("ebn_att_logit_rows_f32", pt(Uu), pt(P.view("u_b")), pt(P.view("u_q")), pt(a_all), n_rows, A, S())
+        self._check_oob()
+        return SimpleNamespace(news_all=news_all, a_all=a_all, n_rows=n_rows)
+
+    def score_cached(self, cache, his_idx, cand_idx, cand_imp, sigmoid=True, return_user=False):
+        """act(news_all[cand_i] . user[cand_imp[i]]) of one indexed batch in ONE launch: his_idx (b, H) / cand_idx (n,) rows of the
+        cache, cand_imp (n,) the impression of each candidate, ascending (an impression's candidates are contiguous)."""
+        his_idx, cand_idx, cand_imp = np.asarray(his_idx), np.asarray(cand_idx).reshape(-1), np.asarray(cand_imp).reshape(-1)
+        if his_idx.ndim != 2 or cand_imp.shape != cand_idx.shape:
+            raise ValueError(f"indexed batches need his_idx (b, H) and one impression per candidate, got {tuple(his_idx.shape)}, "
+                             f"{tuple(cand_idx.shape)}, {tuple(cand_imp.shape)}")
+        if cand_imp.size > 1 and (np.diff(cand_imp) < 0).any():
+            raise ValueError("the candidates of an impression must be contiguous (impression numbers ascending)")
+        B, H, n = his_idx.shape[0], his_idx.shape[1], cand_idx.shape[0]
+        dev = self.device
+        offsets = torch.from_numpy(np.searchsorted(cand_imp, np.arange(B + 1)).astype(np.int64)).to(dev)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        hi, ci = i32(his_idx.reshape(-1)), i32(cand_idx)
+        out = torch.empty(n, device=dev)
+        user = torch.empty(B, self.F, device=dev) if return_user else None
+        _hip.call("ebn_indexed_attpool_score_f32", _hip.ptr(cache.news_all), _hip.ptr(cache.a_all), cache.n_rows, _hip.ptr(hi),
+                  _hip.ptr(ci), _hip.ptr(offsets), n, _hip.ptr(out), _hip.ptr(user), _hip.ptr(self.row_oob_flag), B, H, self.F,
+                  1 if sigmoid else 0, _hip.stream_handle())
+        self._check_oob()
+        return (out, user) if return_user else out
+
     def _check_oob(self):
-        flags = torch.cat([self.oob_flag, self.cat_oob_flag, self.range_flag])
-        oob, coob, rng_bad = (int(v) for v in flags.cpu().tolist())
-        if oob or coob or rng_bad:
+        flags = torch.cat([self.oob_flag, self.cat_oob_flag, self.range_flag, self.row_oob_flag])
+        oob, coob, rng_bad, row_bad = (int(v) for v in flags.cpu().tolist())
+        if oob or coob or rng_bad or row_bad:
             self.oob_flag.zero_()
             self.cat_oob_flag.zero_()
             self.range_flag.zero_()
+            self.row_oob_flag.zero_()
+        if row_bad:
+            raise IndexError("article row out of range for the encoded catalogue")
         if oob:
             raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
         if coob:

@@ -222,6 +222,13 @@ class LSTURDataLoader(NRMSDataLoader):
         lo, hi = self._rows(idx)
         return (self._user_rows(lo, hi),) + tuple(super().compact_eval_batch(idx))
 
+    def user_index_eval_batch(self, idx):
+        """``index_eval_batch`` with the batch's user indexes in front: (user (b,), his (b,H) int32, cand (sum C_i,) int32,
+        impression_of_row (sum C_i,) int32, y (sum C_i, 1)) -- what a scorer that has encoded every article of the matrix once
+        needs per batch when the user encoder also takes the user id."""
+        lo, hi = self._rows(idx)
+        return (self._user_rows(lo, hi),) + tuple(self.index_eval_batch(idx))
+
 
 @dataclass
 class NAMLDataLoader(NewsrecDataLoader):
@@ -318,3 +325,35 @@ class NAMLDataLoader(NewsrecDataLoader):
         rows = np.repeat(np.arange(hi - lo, dtype=np.int32), np.diff(self._inv_off[lo: hi + 1]))
         tm, bm = self.lookup_article_matrix, self.lookup_article_matrix_body
         return (tm[ht], bm[hb], hv[:, :, None], hs[:, :, None], tm[it], bm[ib], iv, is_, rows, ylab.reshape(-1, 1))
+
+    # ---- article catalogue: every distinct (title row, body row, vert, subvert) of the frame, for a scorer that encodes it once --
+    def _build_catalogue(self):
+        cols = [np.concatenate([h, i]).astype(np.int64) for h, i in ((self._his_flat, self._inv_flat), (self._hisb_flat, self._invb_flat),
+                                                                     (self._his_cat[0], self._inv_cat[0]),
+                                                                     (self._his_cat[1], self._inv_cat[1]))]
+        # one int64 key per id: the four values are functions of the article id, so distinct keys <= known articles + the unknown row
+        key = cols[0] * int(self.lookup_article_matrix_body.shape[0]) + cols[1]
+        for c in cols[2:]:  # category values may be any integers: their dense positions go into the key
+            values, pos = np.unique(c, return_inverse=True)
+            key = key * max(len(values), 1) + pos.reshape(-1)
+        _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+        self._catalogue = tuple(c[first] for c in cols[:2]) + tuple(c[first] for c in cols[2:])
+        inv = inv.reshape(-1).astype(np.int32)
+        self._his_cidx, self._inv_cidx = inv[: len(self._his_flat)], inv[len(self._his_flat):]
+
+    def article_catalogue(self):
+        """The distinct articles of the histories and in-view lists as four aligned arrays (title rows of ``lookup_article_matrix``,
+        body rows of ``lookup_article_matrix_body``, vert, subvert), each (n_catalogue,) -- no duplicate rows.  Built on first use."""
+        if getattr(self, "_catalogue", None) is None:
+            self._build_catalogue()
+        return self._catalogue
+
+    def index_eval_batch(self, idx):
+        """Eval batch as row numbers of ``article_catalogue()``: (his (b,H) int32, cand (sum C_i,) int32, impression_of_row
+        (sum C_i,) int32, y (sum C_i, 1)) -- indexing the catalogue's arrays with them gives ``compact_eval_batch``."""
+        self.article_catalogue()
+        lo, hi = self._rows(idx)
+        sl = slice(self._inv_off[lo], self._inv_off[hi])
+        rows = np.repeat(np.arange(hi - lo, dtype=np.int32), np.diff(self._inv_off[lo: hi + 1]))
+        his = self._his_cidx[self._his_off[lo]: self._his_off[hi]].reshape(hi - lo, self._H)
+        return his, self._inv_cidx[sl], rows, self._y_flat[sl].reshape(-1, 1)

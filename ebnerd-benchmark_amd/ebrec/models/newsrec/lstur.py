@@ -78,9 +78,22 @@ class LSTURModel:
 
     def _score_compact(self, user, his, cands, rows) -> torch.Tensor:
         """The same scores for the loader's compact eval layout: user (b,), his (b,H,T) once per impression, cands (n,T),
-        rows[i] = impression of candidate i.  Candidates are encoded per batch (no article cache)."""
+        rows[i] = impression of candidate i.  Every title is encoded per batch (``scorer.cache_articles = False``, or a loader
+        without ``user_index_eval_batch``)."""
         return self._engine.pair_scores(np.asarray(user).reshape(-1), np.asarray(his), np.asarray(cands), np.asarray(rows),
                                         sigmoid=True)
+
+    # -- scorer from a once-encoded catalogue: ScorerModel.predict builds the cache per call (it is valid for the current weights only)
+    _cache_loader_method = "user_index_eval_batch"  # what an eval loader must offer for the cached path (otherwise: per-batch encoding)
+
+    def _build_article_cache(self, loader):
+        """news vectors, GRU input projections and step masks of every row of an eval loader's article matrix."""
+        return self._engine.encode_catalogue(np.asarray(loader.lookup_article_matrix))
+
+    def _score_cached(self, cache, loader, i) -> torch.Tensor:
+        """Scores of eval batch i from the cache: user-table gather, indexed GRU, ragged pair dot."""
+        user, his_idx, cand_idx, rows, _y = loader.user_index_eval_batch(i)
+        return self._engine.score_cached(cache, user, his_idx, cand_idx, rows, sigmoid=True)
 
     def train_step(self, user, his, pred, y):
         """One optimizer step on raw arrays; returns the batch loss (device tensor)."""

@@ -81,8 +81,23 @@ class NAMLModel:
 
     def _score_compact(self, *xs) -> torch.Tensor:
         """The same scores for the loader's compact eval layout: the 4 history arrays once per impression (b,H,.), the 4
-        candidate arrays (n,.), rows[i] = impression of candidate i."""
+        candidate arrays (n,.), rows[i] = impression of candidate i.  Every article is encoded per batch (``scorer.cache_articles =
+        False``, or a loader without an article catalogue)."""
         return self._engine.pair_scores(xs[:4], xs[4:8], np.asarray(xs[8]), sigmoid=True)
+
+    # -- scorer from a once-encoded catalogue: ScorerModel.predict builds the cache per call (it is valid for the current weights only)
+    _cache_loader_method = "article_catalogue"  # what an eval loader must offer for the cached path (otherwise: per-batch encoding)
+
+    def _build_article_cache(self, loader):
+        """news vectors and user-attention logits of every distinct article of an eval loader (``article_catalogue()``)."""
+        t_rows, b_rows, vert, subvert = loader.article_catalogue()
+        return self._engine.encode_catalogue(np.asarray(loader.lookup_article_matrix)[t_rows],
+                                             np.asarray(loader.lookup_article_matrix_body)[b_rows], vert, subvert)
+
+    def _score_cached(self, cache, loader, i) -> torch.Tensor:
+        """Scores of eval batch i from the cache: one indexed pooling-and-scoring launch."""
+        his_idx, cand_idx, rows, _y = loader.index_eval_batch(i)
+        return self._engine.score_cached(cache, his_idx, cand_idx, rows, sigmoid=True)
 
     def train_step(self, *xs):
         """One optimizer step on raw arrays (the 8 inputs and y); returns the batch loss (device tensor)."""

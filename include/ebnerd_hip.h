@@ -706,6 +706,18 @@ int ebn_gru_fwd_f32(const float* gx, const float* X, const float* Wrec, const fl
 int ebn_gru_bwd_f32(const float* dhH, const float* X, const float* Wrec, const float* Hs, const float* act, float* dgx,
                     float* dgh, float* dh0, int64_t B, int32_t H, int32_t F, int32_t U, ebn_stream_t stream);
 
+/* The same recurrence for scorer.predict over a once-encoded article catalogue (lstur.py:81-104,191-200 with the news encoder
+ * taken out of the per-batch work): gx_all [n_rows, 3U] = news_all . kernel of EVERY catalogue row (one ebn_gemm_f32 per predict),
+ * live_all [n_rows] int32 = any(news_all[row] != 0) (the Masking(0.0) predicate of ebn_gru_fwd_f32, per article), his_idx [B, H]
+ * int32 catalogue rows.  Step t of sequence b reads gx_all[his_idx[b, t]] and is masked when live_all says so; one launch per step,
+ * the grid, tile GEMM and gate epilogue of ebn_gru_fwd_f32 (bit-equal to its Hs[H] on the gathered rows).  h moves between h_work
+ * and h_out [B, U] (distinct, neither may be h0); the last step writes h_out.  Nothing is kept for a backward pass.  h0 [B, U] or
+ * NULL (zeros).  A row number outside [0, n_rows) sets *oob_flag (may be NULL), is never used as an address and masks the step.
+ * U % 4 == 0, H <= 4096, Wrec / h0 / h_work / h_out 16-byte aligned.                                                          */
+int ebn_gru_infer_indexed_f32(const float* gx_all, const int32_t* live_all, int64_t n_rows, const int32_t* his_idx,
+                              const float* Wrec, const float* bias, const float* h0, float* h_work, float* h_out, int64_t B,
+                              int32_t H, int32_t U, int32_t* oob_flag, ebn_stream_t stream);
+
 /* ---- NAML (naml.py news encoder: title / body / vert / subvert views, layers.py:55-81 AttLayer2 over the views) -------------
  * Title and body run ebn_gather_rows_f32 -> ebn_conv1d_fwd_f32 (pooling dropout p = 0) -> ebn_attpool_fwd_f32, with their own
  * weights and the shared word table; the title at sites EBN_SITE_NEWS_IN / EBN_SITE_NPA_CONV, the body at the two sites below.
@@ -922,6 +934,26 @@ int ebn_rank_metrics(const void* scores, int32_t score_kind, const uint8_t* labe
  * ANY two equal scores (flag bit 0) or a non-finite score (bit 1) is left to the host: its ranks are written as 0.               */
 int ebn_list_ranks(const void* scores, int32_t score_kind, int64_t n_items, const int64_t* offsets, int64_t n_lists, int32_t form,
                    int32_t* ranks, uint8_t* flags, ebn_stream_t stream);
+
+/* ---- scoring from a once-encoded article catalogue (naml.py user encoder + scorer: AttLayer2 layers.py:55-81, Dot + sigmoid) ---
+ * The NAML user encoder is an UNMASKED AttLayer2 over the history's news vectors: the logit of a history item,
+ * a = exp(tanh(x.W + b).q) (layers.py:69-75, no max-subtraction), depends on the article alone -- one scalar per catalogue row.
+ * a[r] = exp(sum_k tanh(U[r, k] + b[k]) q[k]) for the pre-activations U [n_rows, A] = news_all . W (one ebn_gemm_f32); U is not
+ * modified.  The arithmetic of ebn_attpool_fwd_f32's logit.                                                                    */
+int ebn_att_logit_rows_f32(const float* U, const float* b, const float* q, float* a, int64_t n_rows, int32_t A,
+                           ebn_stream_t stream);
+/* The user stage and the scorer of one eval batch in one launch (layers.py:75-80 + naml.py scorer: sigmoid(news(pred_one) . user)):
+ * one workgroup per impression i of B,
+ *   w_l = a_all[his_idx[i, l]] / (sum_l a_all[his_idx[i, l]] + 1e-7),  user_i = sum_l w_l news_all[his_idx[i, l]]  (kept on chip),
+ *   scores[p] = act(user_i . news_all[cand_idx[p]]) for p in [offsets[i], offsets[i + 1]),  act = sigmoid (mode 1) or id (0).
+ * news_all [n_rows, F], a_all [n_rows], his_idx [B, H] int32, cand_idx [n_cand] int32 with int64 CSR offsets [B + 1] (an
+ * impression's candidates are contiguous), user [B, F] optional (NULL: not written).  Any candidate count per impression, 0
+ * included; H <= 2048, F % 4 == 0, F <= 8192, news_all / user 16-byte aligned.  A row number outside [0, n_rows) sets *oob_flag
+ * (may be NULL) and is never used as an address: a history item of that kind is skipped, a candidate of that kind scores act(0);
+ * an offsets pair that runs backwards or leaves [0, n_cand] makes that impression's list empty.  Fixed summation order.          */
+int ebn_indexed_attpool_score_f32(const float* news_all, const float* a_all, int64_t n_rows, const int32_t* his_idx,
+                                  const int32_t* cand_idx, const int64_t* offsets, int64_t n_cand, float* scores, float* user,
+                                  int32_t* oob_flag, int64_t B, int32_t H, int32_t F, int32_t mode, ebn_stream_t stream);
 
 #ifdef __cplusplus
 }
