@@ -449,23 +449,15 @@ class LSTUREngine:
         self._check_oob()
         return SimpleNamespace(news_all=news_all, gx_all=gx_all, live=live, n_rows=n_rows)
 
-    def score_cached(self, cache, user, his_idx, cand_idx, cand_imp, sigmoid=True):
-        """act(news_all[cand_i] . user[cand_imp[i]]) of one indexed batch: user (b,) user indexes, his_idx (b, H) / cand_idx (n,) rows
-        of the cache, cand_imp (n,) the impression of each candidate.  User-table gather -> indexed GRU over the cached input
-        projections -> ("con") Dense -> ragged pair dot against the cached news vectors."""
-        user = self._uidx(user)
-        his_idx, cand_idx = np.asarray(his_idx), np.asarray(cand_idx).reshape(-1)
-        if his_idx.ndim != 2 or user.shape[0] != his_idx.shape[0]:
-            raise ValueError(f"indexed batches need user (b,) and his_idx (b, H), got {tuple(user.shape)} {tuple(his_idx.shape)}")
-        self._host_ranges(user)
-        if cand_idx.size and (cand_idx.min() < 0 or cand_idx.max() >= cache.n_rows):
-            raise IndexError(f"article row out of range [0, {cache.n_rows}) for the encoded catalogue")
+    def _user_vectors_indexed(self, cache, user, his_idx):
+        """The user half of the cached scorer, launches only: user (b,) user indexes, his_idx (b, H) rows of the cache -> (b, F).
+        User-table gather -> indexed GRU over the cached input projections -> ("con") Dense."""
         S = _hip.stream_handle
         call, pt = _hip.call, _hip.ptr
-        B, H, n, U = his_idx.shape[0], his_idx.shape[1], cand_idx.shape[0], self.U
+        B, H, U = his_idx.shape[0], his_idx.shape[1], self.U
         dev = self.device
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        uidx, hi, ci, ui = i32(user), i32(his_idx.reshape(-1)), i32(cand_idx), i32(np.asarray(cand_imp).reshape(-1))
+        uidx, hi = i32(user), i32(his_idx.reshape(-1))
         Eu, h_work, h_out = (torch.empty(B, U, device=dev) for _ in range(3))
         call("ebn_gather_rows_f32", pt(uidx), pt(self.user_table), pt(Eu), B, U, self.n_users + 1, None, -1, ctypes.c_float(0.0),
              pt(self.user_oob_flag), S())
@@ -476,8 +468,38 @@ class LSTUREngine:
         if self.type == "con":
             user_vec = torch.empty(B, U, device=dev)
             self._con_dense(h_out, Eu, user_vec, torch.ones(max(B, 1), device=dev), B)
-        out = torch.empty(n, device=dev)
-        call("ebn_pair_score_f32", pt(user_vec), pt(cache.news_all), pt(ui), pt(ci), pt(out), n, self.F, 1 if sigmoid else 0, S())
+        return user_vec
+
+    def _indexed_users_args(self, user, his_idx):
+        user = self._uidx(user)
+        his_idx = np.asarray(his_idx)
+        if his_idx.ndim != 2 or user.shape[0] != his_idx.shape[0]:
+            raise ValueError(f"indexed batches need user (b,) and his_idx (b, H), got {tuple(user.shape)} {tuple(his_idx.shape)}")
+        self._host_ranges(user)
+        return user, his_idx
+
+    def user_vectors_cached(self, cache, user, his_idx):
+        """user vectors (b, F) of one indexed batch from the cache (recommend): the user half of ``score_cached``."""
+        user, his_idx = self._indexed_users_args(user, his_idx)
+        user_vec = self._user_vectors_indexed(cache, user, his_idx)
+        self._check_oob()
+        return user_vec
+
+    def score_cached(self, cache, user, his_idx, cand_idx, cand_imp, sigmoid=True):
+        """act(news_all[cand_i] . user[cand_imp[i]]) of one indexed batch: user (b,) user indexes, his_idx (b, H) / cand_idx (n,) rows
+        of the cache, cand_imp (n,) the impression of each candidate.  User-table gather -> indexed GRU over the cached input
+        projections -> ("con") Dense -> ragged pair dot against the cached news vectors."""
+        user, his_idx = self._indexed_users_args(user, his_idx)
+        cand_idx = np.asarray(cand_idx).reshape(-1)
+        if cand_idx.size and (cand_idx.min() < 0 or cand_idx.max() >= cache.n_rows):
+            raise IndexError(f"article row out of range [0, {cache.n_rows}) for the encoded catalogue")
+        n = cand_idx.shape[0]
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        user_vec = self._user_vectors_indexed(cache, user, his_idx)
+        ci, ui = i32(cand_idx), i32(np.asarray(cand_imp).reshape(-1))
+        out = torch.empty(n, device=self.device)
+        _hip.call("ebn_pair_score_f32", _hip.ptr(user_vec), _hip.ptr(cache.news_all), _hip.ptr(ui), _hip.ptr(ci), _hip.ptr(out), n,
+                  self.F, 1 if sigmoid else 0, _hip.stream_handle())
         self._check_oob()
         return out
 

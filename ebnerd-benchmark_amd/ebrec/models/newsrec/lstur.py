@@ -17,6 +17,7 @@ import torch
 
 from ._engine import glorot_uniform_np
 from ._engine_lstur import LSTUREngine
+from ._recommend import recommend
 from ._keras_like import ScorerModel, TrainModel
 
 
@@ -94,6 +95,24 @@ class LSTURModel:
         """Scores of eval batch i from the cache: user-table gather, indexed GRU, ragged pair dot."""
         user, his_idx, cand_idx, rows, _y = loader.user_index_eval_batch(i)
         return self._engine.score_cached(cache, user, his_idx, cand_idx, rows, sigmoid=True)
+
+    # -- top-N lists from the once-encoded catalogue (_recommend.py) ------------------------------------------------------------
+    _recommend_loader_method = "user_index_eval_batch"
+
+    def _recommend_index(self, loader):
+        return loader.lookup_article_index
+
+    def _recommend_cache(self, loader):
+        cache = self._build_article_cache(loader)
+        return cache, cache.news_all
+
+    def _user_vectors_cached(self, cache, loader, i):
+        user, his_idx = loader.user_index_eval_batch(i)[:2]
+        return self._engine.user_vectors_cached(cache, user, his_idx), his_idx
+
+    def recommend(self, loader, candidate_ids=None, **kwargs):
+        """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
+        return recommend(self, loader, candidate_ids, **kwargs)
 
     def train_step(self, user, his, pred, y):
         """One optimizer step on raw arrays; returns the batch loss (device tensor)."""

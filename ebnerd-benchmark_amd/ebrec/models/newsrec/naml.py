@@ -19,6 +19,7 @@ import torch
 
 from ._engine import glorot_uniform_np
 from ._engine_naml import NAMLEngine
+from ._recommend import recommend
 from ._keras_like import ScorerModel, TrainModel
 
 
@@ -98,6 +99,31 @@ class NAMLModel:
         """Scores of eval batch i from the cache: one indexed pooling-and-scoring launch."""
         his_idx, cand_idx, rows, _y = loader.index_eval_batch(i)
         return self._engine.score_cached(cache, his_idx, cand_idx, rows, sigmoid=True)
+
+    # -- top-N lists from the once-encoded catalogue (_recommend.py) ------------------------------------------------------------
+    _recommend_loader_method = "article_catalogue"
+
+    def _recommend_index(self, loader):
+        """The cache's rows are those of ``article_catalogue()``: an article id is a candidate when its title row is in it
+        (the unknown title, row 0, may stand for several catalogue rows and belongs to no id)."""
+        t_rows = np.asarray(loader.article_catalogue()[0])
+        row_of_title = {int(t): r for r, t in enumerate(t_rows.tolist()) if t != 0}
+        return {k: row_of_title[t] for k, t in loader.lookup_article_index.items() if t in row_of_title}
+
+    def _recommend_cache(self, loader):
+        cache = self._build_article_cache(loader)
+        return cache, cache.news_all
+
+    def _user_vectors_cached(self, cache, loader, i):
+        his_idx = loader.index_eval_batch(i)[0]
+        none = np.zeros(0, np.int32)
+        _scores, user = self._engine.score_cached(cache, his_idx, none, none, sigmoid=True, return_user=True)
+        return user, his_idx
+
+    def recommend(self, loader, candidate_ids=None, **kwargs):
+        """Each impression's top_n of one shared candidate list (``_recommend.recommend``): the candidates are articles of the
+        loader's catalogue, i.e. of its histories and in-view lists."""
+        return recommend(self, loader, candidate_ids, **kwargs)
 
     def train_step(self, *xs):
         """One optimizer step on raw arrays (the 8 inputs and y); returns the batch loss (device tensor)."""

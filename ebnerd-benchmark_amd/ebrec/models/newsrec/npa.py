@@ -80,6 +80,10 @@ class NPAModel:
         return self._engine.pair_scores(np.asarray(user).reshape(-1), np.asarray(his), np.asarray(cands), np.asarray(rows),
                                         sigmoid=True)
 
+    def recommend(self, loader, candidate_ids=None, **kwargs):
+        raise NotImplementedError("NPAModel.recommend: NPA's news vector depends on the user (personalised attention, npa.py), so "
+                                  "there is no per-article catalogue to rank against")
+
     def train_step(self, user, his, pred, y):
         """One optimizer step on raw arrays; returns the batch loss (device tensor)."""
         return self._engine.train_step(user, his, pred, y)

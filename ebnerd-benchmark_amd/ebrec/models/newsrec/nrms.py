@@ -25,6 +25,7 @@ import torch
 from ebrec import _hip
 
 from ._engine import NRMSEngine, glorot_uniform_np
+from ._recommend import recommend
 from ._keras_like import EncoderModel, ScorerModel, TrainModel, dedup_rows
 
 WEIGHT_NAMES = ["news.emb", "news.attn.WQ", "news.attn.WK", "news.attn.WV", "news.att.W", "news.att.b", "news.att.q",
@@ -125,18 +126,41 @@ class NRMSModel:
         """news vectors (n_articles+1, E) of every row of a loader's token matrix, on the device."""
         return self._engine.encode_news(np.asarray(matrix))
 
+    def _users_indexed(self, news_all: torch.Tensor, his_idx) -> torch.Tensor:
+        """user vectors (b, E) of one eval batch from cached news vectors: his_idx (b,H) are rows of news_all."""
+        eng = self._engine
+        hi = torch.from_numpy(np.ascontiguousarray(np.asarray(his_idx).reshape(-1), dtype=np.int32)).to(eng.device)
+        b, H = len(his_idx), np.asarray(his_idx).shape[1]  # H from the batch: the history-length sweep scores truncated histories
+        NEh = torch.empty(b * H, eng.E, device=eng.device)
+        _hip.call("ebn_gather_rows_f32", _hip.ptr(hi), _hip.ptr(news_all), _hip.ptr(NEh), b * H, eng.E, news_all.shape[0],
+                  None, -1, ctypes.c_float(0.0), None, _hip.stream_handle())
+        return eng.encode_users_from_news(NEh.view(b, H, eng.E))
+
     def _score_indexed(self, news_all: torch.Tensor, his_idx, cand_idx, rows) -> torch.Tensor:
         """Scores of one eval batch from cached news vectors: his_idx (b,H) / cand_idx (n,) are rows of news_all,
         rows[i] = impression of candidate i."""
         eng = self._engine
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(eng.device)
-        hi = dev(np.asarray(his_idx).reshape(-1))
-        b, H = len(his_idx), np.asarray(his_idx).shape[1]  # H from the batch: the history-length sweep scores truncated histories
-        NEh = torch.empty(b * H, eng.E, device=eng.device)
-        _hip.call("ebn_gather_rows_f32", _hip.ptr(hi), _hip.ptr(news_all), _hip.ptr(NEh), b * H, eng.E, news_all.shape[0],
-                  None, -1, ctypes.c_float(0.0), None, _hip.stream_handle())
-        user = eng.encode_users_from_news(NEh.view(b, H, eng.E))
+        user = self._users_indexed(news_all, his_idx)
         return eng.pair_scores(user, news_all, dev(rows), dev(cand_idx), sigmoid=True)
+
+    # -- top-N lists from the once-encoded catalogue (_recommend.py) ------------------------------------------------------------
+    _recommend_loader_method = "index_eval_batch"
+
+    def _recommend_index(self, loader):
+        return loader.lookup_article_index
+
+    def _recommend_cache(self, loader):
+        news_all = self._encode_article_matrix(loader.lookup_article_matrix)
+        return news_all, news_all
+
+    def _user_vectors_cached(self, cache, loader, i):
+        his_idx = loader.index_eval_batch(i)[0]
+        return self._users_indexed(cache, his_idx), his_idx
+
+    def recommend(self, loader, candidate_ids=None, **kwargs):
+        """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
+        return recommend(self, loader, candidate_ids, **kwargs)
 
     # -- interchange ------------------------------------------------------------------
     def from_keras_weight_list(self, weights):

@@ -18,6 +18,7 @@ import torch
 from ebrec import _hip
 
 from ._engine_docvec import DocVecEngine
+from ._recommend import recommend
 from ._keras_like import EncoderModel, ScorerModel, TrainModel, dedup_rows
 
 
@@ -81,16 +82,39 @@ class NRMSDocVec:
         """news vectors (n_articles+1, E) of every document vector of a loader's matrix, on the device."""
         return self._engine.encode_news(np.asarray(matrix, dtype=np.float32))
 
-    def _score_indexed(self, news_all: torch.Tensor, his_idx, cand_idx, rows) -> torch.Tensor:
+    def _users_indexed(self, news_all: torch.Tensor, his_idx) -> torch.Tensor:
+        """user vectors (b, E) of one eval batch from cached news vectors: his_idx (b,H) are rows of news_all."""
         eng = self._engine
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(eng.device)
-        hi = dev(np.asarray(his_idx).reshape(-1))
+        hi = torch.from_numpy(np.ascontiguousarray(np.asarray(his_idx).reshape(-1), dtype=np.int32)).to(eng.device)
         b, H = len(his_idx), np.asarray(his_idx).shape[1]  # H from the batch: the history-length sweep scores truncated histories
         NEh = torch.empty(b * H, eng.E, device=eng.device)
         _hip.call("ebn_gather_rows_f32", _hip.ptr(hi), _hip.ptr(news_all), _hip.ptr(NEh), b * H, eng.E, news_all.shape[0],
                   None, -1, ctypes.c_float(0.0), None, _hip.stream_handle())
-        user = eng.encode_users_from_news(NEh.view(b, H, eng.E))
+        return eng.encode_users_from_news(NEh.view(b, H, eng.E))
+
+    def _score_indexed(self, news_all: torch.Tensor, his_idx, cand_idx, rows) -> torch.Tensor:
+        eng = self._engine
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(eng.device)
+        user = self._users_indexed(news_all, his_idx)
         return eng.pair_scores(user, news_all, dev(rows), dev(cand_idx), sigmoid=True)
+
+    # -- top-N lists from the once-encoded catalogue (_recommend.py) ------------------------------------------------------------
+    _recommend_loader_method = "index_eval_batch"
+
+    def _recommend_index(self, loader):
+        return loader.lookup_article_index
+
+    def _recommend_cache(self, loader):
+        news_all = self._encode_article_matrix(loader.lookup_article_matrix)
+        return news_all, news_all
+
+    def _user_vectors_cached(self, cache, loader, i):
+        his_idx = loader.index_eval_batch(i)[0]
+        return self._users_indexed(cache, his_idx), his_idx
+
+    def recommend(self, loader, candidate_ids=None, **kwargs):
+        """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
+        return recommend(self, loader, candidate_ids, **kwargs)
 
     def train_step(self, his, pred, y):
         return self._engine.train_step(his, pred, y)

@@ -955,6 +955,35 @@ int ebn_indexed_attpool_score_f32(const float* news_all, const float* a_all, int
                                   const int32_t* cand_idx, const int64_t* offsets, int64_t n_cand, float* scores, float* user,
                                   int32_t* oob_flag, int64_t B, int32_t H, int32_t F, int32_t mode, ebn_stream_t stream);
 
+/* ---- top-N recommendation from an encoded catalogue (examples/beyond_accuracy/make_beyond_accuracy.ipynb, cell "Your Model":
+ * every beyond-accuracy user's top-N out of one shared candidate list; scorers of nrms.py / nrms_docvec.py / lstur.py / naml.py:
+ * act(user . news)) ---------------------------------------------------------------------------------------------------------------
+ * score[u, c] = users[u, :] . news_all[cand_rows[c], :] in exact fp32 (MFMA fma chain), never written out: each user keeps its best
+ * k in the order (score descending, candidate position ascending).  users [U, F], news_all [n_rows, F]; cand_rows [M] rows of
+ * news_all, or NULL = rows 0 .. n_rows - 1 (then M == n_rows); duplicate rows are distinct candidates.  exclude [U, X] (or NULL):
+ * candidate c is skipped for user u when cand_rows[c] equals any of exclude[u, :]; entries outside [0, n_rows) match nothing (-1 is
+ * the padding).  A cand_rows entry outside [0, n_rows) is never turned into an address: it is skipped and sets flags[0]; a NaN score
+ * never enters a list and sets flags[1]; +-inf rank like numbers.  flags [2] is only ever SET (the caller zeroes it and may let it
+ * accumulate over calls).  out_pos [U, k]: position in cand_rows (the row number when cand_rows is NULL), -1 in the empty trailing
+ * slots of a user with fewer than k admissible candidates; out_score [U, k]: the raw dot product (mode 0) or its sigmoid (mode 1,
+ * applied to the kept values only; ranking is always on the raw value), -inf in empty slots.
+ * Limits: 1 <= k <= 64, 0 <= X <= 256, F % 4 == 0, 4 <= F <= 8192 (EBN_ERR_UNSUPPORTED), users / news_all 16-byte aligned
+ * (EBN_ERR_ALIGN).  U == 0: nothing to do; M == 0: the outputs are filled as empty.
+ * The grid is 128-user tiles x n_splits ranges of 128-candidate tiles (n_splits 0 = ebn_topk_auto_splits; clamped to the number of
+ * candidate tiles and to 64).  More than one range: each writes a partial list to the workspace (16-byte aligned, at least
+ * ebn_topk_workspace_bytes(U, k, n_splits) bytes, else EBN_ERR_BAD_ARG) and a second launch merges them in the same total order.
+ * No atomics; the result is bit-identical for every n_splits and from run to run.                                                 */
+/* Bytes of workspace for n_splits >= 1 candidate ranges (a nominal 16 for one range, which needs none); 0 for sizes outside the
+ * limits.  Pure host query.                                                                                                       */
+int64_t ebn_topk_workspace_bytes(int64_t n_users, int32_t k, int32_t n_splits);
+/* The number of candidate ranges n_splits = 0 stands for: 1 once the user tiles alone give a few hundred workgroups.  Pure host
+ * query, >= 1.                                                                                                                    */
+int ebn_topk_auto_splits(int64_t n_users, int64_t n_cand);
+int ebn_topk_score_f32(const float* users, const float* news_all, int64_t n_rows, const int32_t* cand_rows, int64_t M,
+                       const int32_t* exclude, int32_t X, int32_t k, int32_t mode, int32_t n_splits, int32_t* out_pos,
+                       float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, int32_t F,
+                       ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
