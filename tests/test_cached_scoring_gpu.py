@@ -10,6 +10,7 @@ import torch
 
 from tests import lstur_oracle as lo
 from tests import naml_oracle as nao
+from tests.guarded import guard_in
 from tests.hip_testutil import P, S, assert_close, dev, host
 from tests.test_data_pipeline import frames  # noqa: F401  (the fixture parquets under tests/golden/ebnerd)
 from tests.test_lstur_gpu import _model as lstur_model
@@ -137,13 +138,8 @@ def _pool_ref(news, a, his, cand, off, sigmoid):
 
 
 def _guarded(x):
-    """x on the device as the LAST bytes of its allocation, behind a NaN guard: a read in front of the rows poisons the result, and
-    nothing of the allocation lies behind them."""
-    flat = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
-    guard = 4096
-    buf = torch.full((guard + flat.size,), float("nan"), device="cuda")
-    buf[guard:].copy_(torch.from_numpy(flat))
-    return buf[guard:].view(*x.shape)  # the view keeps the allocation alive
+    """x on the device between two NaN guards (tests/guarded.py): a read in front of or behind the rows poisons the result."""
+    return guard_in(np.asarray(x, dtype=np.float32))[0]  # the view keeps the allocation alive
 
 
 def _pool_run(hip, news_d, a_d, n_rows, his, cand, off, F, mode, want_user):
