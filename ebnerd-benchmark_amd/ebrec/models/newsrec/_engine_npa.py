@@ -5,7 +5,9 @@ Per impression b with user index u_b (npa.py:60-190):
   title of impression b:  X = Dropout(p)(emb[tokens]) -> Vd = Dropout(0.2)(Dropout(p)(relu(conv1d_same(X) + b_c)))
                           -> U = tanh(Vd.Wa + ba), w = softmax_l(qn_b . U_l), news = sum_l w_l Vd_l
   user_b = PAP_u(Dropout(0.2)(news of the H history titles), qu_b);  scores = cand . user_b -> softmax + compiled loss
-Candidates are encoded with their impression's query, so there is no article cache: every title is encoded per impression.
+Candidates are encoded with their impression's query, so a training step encodes every title per impression.  At inference
+the user reaches a title only through the logits qn_b . U_l: Vd and U are per article, and scorer.predict keeps them per row of
+the loader's article matrix (encode_catalogue) and pools each (impression, article) pair from them (score_cached).
 
 Data layout in HBM (fp32 row-major):
   table        (V, E)              word embeddings (trainable: fixed-point gradient accumulator + fused Adam sweep)
@@ -18,6 +20,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -104,6 +107,7 @@ class NPAEngine:
         self.oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.user_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.row_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)  # a row outside an encoded catalogue
         self.loss_dev = torch.zeros(1, device=dev)
         st = _hip.StepState()
         st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
@@ -372,13 +376,95 @@ class NPAEngine:
                   1 if sigmoid else 0, _hip.stream_handle())
         return out
 
+    # ------------------------------------------------------------------ scoring from a once-encoded catalogue
+    def catalogue_bytes(self, n_rows) -> int:
+        """HBM bytes of encode_catalogue()'s two arrays for n_rows titles: n_rows * T * (F + A) fp32."""
+        return int(n_rows) * self.T * (self.F + self.A) * 4
+
+    def encode_catalogue(self, tokens, chunk=4096):
+        """Everything the news encoder computes from the article alone, for the CURRENT weights (build it per predict, never keep it
+        on the model): tokens (n_rows, T) -> cache with Vd_all (n_rows, T, F) = relu(conv1d_same(emb[tokens]) + b_c) and
+        Ua_all (n_rows, T, A) = tanh(Vd.Wa + ba), inference mode (no dropout).  The user enters the news vector only through the
+        logits q . Ua_l, which score_cached computes.  Encoded in chunks: the gathered-token scratch is that of `chunk` titles
+        whatever n_rows is; the conv and the attention GEMM write straight into the chunk's slices."""
+        tokens = np.asarray(tokens)
+        if tokens.ndim != 2 or tokens.shape[1] != self.T:
+            raise ValueError(f"catalogue tokens must be (n_rows, {self.T}), got {tuple(tokens.shape)}")
+        self._host_ranges(np.zeros(0, np.int64), tokens)
+        S = _hip.stream_handle
+        call, pt, P = _hip.call, _hip.ptr, self.params
+        f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
+        n_rows, T, E, F, A = tokens.shape[0], self.T, self.E, self.F, self.A
+        dev = self.device
+        Vd_all, Ua_all = torch.empty(n_rows, T, F, device=dev), torch.empty(n_rows, T, A, device=dev)
+        chunk = max(1, min(int(chunk), n_rows))
+        ids, X = torch.empty(chunk * T, dtype=torch.int32, device=dev), torch.empty(chunk * T, E, device=dev)
+        Wb = P.view("conv_Wb")
+        for s in range(0, n_rows, chunk):
+            n = min(chunk, n_rows - s)
+            R = n * T
+            self._put(ids[:R], tokens[s:s + n])
+            call("ebn_gather_rows_f32", pt(ids), pt(self.table), pt(X), R, E, self.V, None, -1, f0, pt(self.oob_flag), S())
+            call("ebn_conv1d_fwd_f32", pt(X), pt(Wb), pt(Wb[self.window * E]), pt(Vd_all[s]), n, T, E, F, self.window, None, -1, f0,
+                 SITE_NEWS_PAP, f0, S())
+            call("ebn_gemm_f32", 0, 0, R, A, F, f1, pt(Vd_all[s]), F, pt(P.view("n_Wa")), A, f0, pt(Ua_all[s]), A, S())
+            call("ebn_bias_tanh_rows_f32", pt(Ua_all[s]), pt(P.view("n_ba")), R, A, S())
+        self._check_oob()
+        return SimpleNamespace(Vd_all=Vd_all, Ua_all=Ua_all, n_rows=n_rows)
+
+    def score_cached(self, cache, user, his_idx, cand_idx, cand_imp, sigmoid=True):
+        """act(news(cand_i | user[cand_imp[i]]) . user_vec[cand_imp[i]]) of one indexed batch: user (b,) user indexes, his_idx (b, H) /
+        cand_idx (n,) rows of the cache, cand_imp (n,) the impression of each candidate.  User-table gather -> the two query
+        Dense -> indexed pooling of the b*H history slots -> the user stage of _encode, unchanged -> indexed pooling of the
+        candidates fused with the score (the candidate vectors are not written)."""
+        user = self._uidx(user)
+        his_idx = np.asarray(his_idx)
+        if his_idx.ndim != 2 or his_idx.shape[1] != self.H or user.shape[0] != his_idx.shape[0]:
+            raise ValueError(f"indexed batches need user (b,) and his_idx (b, {self.H}), got {tuple(user.shape)} {tuple(his_idx.shape)}")
+        self._host_ranges(user)
+        cand_idx, cand_imp = np.asarray(cand_idx).reshape(-1), np.asarray(cand_imp).reshape(-1)
+        if cand_idx.shape != cand_imp.shape:
+            raise ValueError(f"one impression per candidate: {cand_idx.shape} vs {cand_imp.shape}")
+        if cand_imp.size and (cand_imp.min() < 0 or cand_imp.max() >= his_idx.shape[0]):
+            raise IndexError(f"candidate impression out of range [0, {his_idx.shape[0]})")
+        S = _hip.stream_handle
+        call, pt, P = _hip.call, _hip.ptr, self.params
+        f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
+        B, n, T, F, A, Du, H = his_idx.shape[0], cand_idx.shape[0], self.T, self.F, self.A, self.Du, self.H
+        dev = self.device
+        f = lambda *s: torch.empty(*s, device=dev)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        uidx, hi, ci, rows = i32(user), i32(his_idx.reshape(-1)), i32(cand_idx), i32(cand_imp)
+        q_his = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(H)
+        iota = torch.arange(B, dtype=torch.int32, device=dev)
+        Eu, Qn, Qu, ones = f(B, Du), f(B, A), f(B, A), torch.ones(max(B, 1), device=dev)
+        NV_h, Uu, wu, user_vec, out = f(B * H, F), f(B * H, A), f(B * H), f(B, F), f(n)
+        call("ebn_gather_rows_f32", pt(uidx), pt(self.user_table), pt(Eu), B, Du, self.n_users + 1, None, -1, f0,
+             pt(self.user_oob_flag), S())
+        for Q, Wq, bq in ((Qn, "n_Wq", "n_bq"), (Qu, "u_Wq", "u_bq")):  # Dense(A)(u_emb) = 1.bq + e.Wq, as _encode
+            call("ebn_gemm_f32", 0, 0, B, A, 1, f1, pt(ones), 1, pt(P.view(bq)), A, f0, pt(Q), A, S())
+            call("ebn_gemm_f32", 0, 0, B, A, Du, f1, pt(Eu), Du, pt(P.view(Wq)), A, f1, pt(Q), A, S())
+        call("ebn_pap_indexed_f32", pt(cache.Ua_all), pt(cache.Vd_all), cache.n_rows, pt(hi), pt(Qn), pt(q_his), B, pt(NV_h), None,
+             None, 0, pt(self.row_oob_flag), B * H, T, F, A, S())
+        call("ebn_gemm_f32", 0, 0, B * H, A, F, f1, pt(NV_h), F, pt(P.view("u_Wa")), A, f0, pt(Uu), A, S())
+        call("ebn_pap_fwd_f32", pt(Uu), pt(P.view("u_ba")), pt(Qu), pt(iota), B, pt(NV_h), pt(user_vec), pt(wu), None, 0, B, H, F, A,
+             None, -1, f0, S())
+        if n:
+            call("ebn_pap_indexed_f32", pt(cache.Ua_all), pt(cache.Vd_all), cache.n_rows, pt(ci), pt(Qn), pt(rows), B, None, pt(user_vec),
+                 pt(out), 1 if sigmoid else 0, pt(self.row_oob_flag), n, T, F, A, S())
+        self._check_oob()
+        return out
+
     def _check_oob(self):
-        flags = torch.cat([self.oob_flag, self.user_oob_flag, self.range_flag])
-        oob, uoob, rng_bad = (int(v) for v in flags.cpu().tolist())
-        if oob or uoob or rng_bad:
+        flags = torch.cat([self.oob_flag, self.user_oob_flag, self.range_flag, self.row_oob_flag])
+        oob, uoob, rng_bad, row_bad = (int(v) for v in flags.cpu().tolist())
+        if oob or uoob or rng_bad or row_bad:
             self.oob_flag.zero_()
             self.user_oob_flag.zero_()
             self.range_flag.zero_()
+            self.row_oob_flag.zero_()
+        if row_bad:
+            raise IndexError("article row out of range for the encoded catalogue")
         if uoob:
             raise IndexError(f"user index out of range [0, {self.n_users}] for the user embedding table")
         if oob:

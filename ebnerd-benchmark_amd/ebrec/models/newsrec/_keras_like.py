@@ -362,13 +362,14 @@ class ScorerModel:
         indexed = getattr(data, "index_eval_batch", None) if compact is not None else None
         if (indexed is not None and self.cache_articles and hasattr(self._owner, "_build_article_cache")
                 and hasattr(data, getattr(self._owner, "_cache_loader_method", "index_eval_batch"))):
-            # LSTUR / NAML: everything that depends on the article alone (news vector, GRU input projection and step mask, user
-            # attention logit) is computed ONCE per predict() -- the cache is valid for the current weights only and is dropped
-            # on return; a batch then costs index-driven row reads (and the recurrent half of the GRU)
+            # LSTUR / NAML / NPA: everything that depends on the article alone (news vector, GRU input projection and step mask, user
+            # attention logit; NPA: conv output and attention keys) is computed ONCE per predict() -- the cache is valid for the
+            # current weights only and is dropped on return; a batch then costs index-driven row reads (and the recurrent half of the GRU)
             cache = self._owner._build_article_cache(data)
-            for i in range(len(data)):
-                outs.append(self._owner._score_cached(cache, data, i).cpu().numpy().reshape(-1, 1))
-            return np.concatenate(outs, axis=0) if outs else np.zeros((0, 1), np.float32)
+            if cache is not None:  # None: the catalogue is over the model's memory budget (NPA) -- per-batch encoding below
+                for i in range(len(data)):
+                    outs.append(self._owner._score_cached(cache, data, i).cpu().numpy().reshape(-1, 1))
+                return np.concatenate(outs, axis=0) if outs else np.zeros((0, 1), np.float32)
         if indexed is not None and self.cache_articles and hasattr(self._owner, "_score_indexed"):
             # every article of the loader's matrix is encoded ONCE (the weights do not change during predict); a batch
             # then costs one user-encoder pass over gathered news vectors and a ragged pair-dot

@@ -8,7 +8,11 @@ Inputs are ``(user_indexes (B,1), his_input_title (B,H,T), pred_input_title (B,C
 (npa.py:196 ``keras.Model([user_indexes, his_input_title, pred_input_title], preds)``).  Deliberate differences:
   * one GPU, through libebnerd_hip.so only (RuntimeError otherwise -- no CPU fallback, no multi-rank form);
   * dropout uses the build's counter-based stream, not TF's (statistical parity only);
-  * weights are saved as a named torch file (``model.model.save_weights``); TF weight lists are not imported.
+  * weights are saved as a named torch file (``model.model.save_weights``); TF weight lists are not imported;
+  * ``scorer.predict`` over an eval-mode loader encodes the loader's article matrix ONCE per call: the conv output ``Vd`` and the
+    attention keys ``Ua = tanh(Vd.Wa + ba)`` of a title do not depend on the user (only the logits ``q(user) . Ua_l`` do), so a
+    batch is scored from row numbers by an indexed pooling kernel.  ``scorer.cache_articles = False`` is the per-batch path, and a
+    catalogue above ``NPAModel.catalogue_max_bytes`` takes it too.
 """
 from __future__ import annotations
 
@@ -80,7 +84,30 @@ class NPAModel:
         return self._engine.pair_scores(np.asarray(user).reshape(-1), np.asarray(his), np.asarray(cands), np.asarray(rows),
                                         sigmoid=True)
 
+    # -- scorer from a once-encoded catalogue: ScorerModel.predict builds the cache per call (it is valid for the current weights only)
+    _cache_loader_method = "user_index_eval_batch"  # what an eval loader must offer for the cached path (otherwise: per-batch encoding)
+    # the catalogue is T * (F + A) floats per article (72 KB at npa-c1, against 1.6 KB for a news vector): the default holds
+    # ebnerd_large (about 125 k articles, 9 GB) and nothing unbounded; above it predict() encodes per batch
+    catalogue_max_bytes = 16 * 2 ** 30
+
+    def _build_article_cache(self, loader):
+        """Conv output and tanh'd attention keys of every row of an eval loader's article matrix; None when they would not fit
+        ``catalogue_max_bytes`` (ScorerModel.predict then takes the per-batch path)."""
+        tokens = np.asarray(loader.lookup_article_matrix)
+        if self._engine.catalogue_bytes(tokens.shape[0]) > self.catalogue_max_bytes:
+            return None
+        return self._engine.encode_catalogue(tokens)
+
+    def _score_cached(self, cache, loader, i) -> torch.Tensor:
+        """Scores of eval batch i from the cache: user-table gather, query Dense, indexed pooling of the history, user stage,
+        indexed pooling of the candidates fused with the score."""
+        user, his_idx, cand_idx, rows, _y = loader.user_index_eval_batch(i)
+        return self._engine.score_cached(cache, user, his_idx, cand_idx, rows, sigmoid=True)
+
     def recommend(self, loader, candidate_ids=None, **kwargs):
+        """Not implemented.  The encoded catalogue of ``scorer.predict`` does not give a per-article vector to rank against: with a
+        shared candidate list the score of a (user, candidate) pair is sum_l w_l (u . Vd_l) with user-dependent w, about
+        T * (F + A) MACs (36 kFLOP at npa-c1) per pair -- a different kernel from the top-k over news vectors of ``_recommend.py``."""
         raise NotImplementedError("NPAModel.recommend: NPA's news vector depends on the user (personalised attention, npa.py), so "
                                   "there is no per-article catalogue to rank against")
 

@@ -955,6 +955,25 @@ int ebn_indexed_attpool_score_f32(const float* news_all, const float* a_all, int
                                   const int32_t* cand_idx, const int64_t* offsets, int64_t n_cand, float* scores, float* user,
                                   int32_t* oob_flag, int64_t B, int32_t H, int32_t F, int32_t mode, ebn_stream_t stream);
 
+/* ---- NPA from a once-encoded catalogue (npa.py:120-136 news encoder, layers.py:312-339 PersonalizedAttentivePooling) ----------
+ * The personalised news vector depends on the user only through the logits q . Ua_l: per catalogue row the conv output
+ * Vd [L, F] and the attention keys Ua = tanh(Vd.Wa + ba) [L, A] are kept, and a (query, article) pair is pooled from them.
+ * U <- tanh(U + ba[k]) in place for U [n_rows, A] (the pre-activations Vd.Wa of ebn_gemm_f32): pap_fwd's expression (layers.py:333),
+ * so the stored bits are those ebn_pap_fwd_f32 leaves in U.                                                                     */
+int ebn_bias_tanh_rows_f32(float* U, const float* ba, int64_t n_rows, int32_t A, ebn_stream_t stream);
+/* One workgroup per sequence n of n_seq, row = row_idx[n] (DEVICE int32), q = Q[q_idx[n]] (Q [n_q, A], q_idx as ebn_pap_fwd_f32:
+ * an index outside [0, n_q) reads row 0):
+ *   s_l = q . Ua_all[row, l];  w = softmax_l(s) (max-subtracted, layers.py:334-335);  pooled = sum_l w_l Vd_all[row, l]
+ *   out[n] = pooled (out [n_seq, F], may be NULL);  scores[n] = act(pooled . users[q_idx[n]]) (users [n_q, F]; scores may be NULL,
+ *   it needs users; act = sigmoid (mode 1) or id (0); npa.py:188-199 scorer) -- with scores alone the vector never reaches memory.
+ * Same operations in the same order as ebn_pap_fwd_f32: given the same Ua and Vd bits, out is bit-equal to that kernel's on
+ * the gathered rows.  Nothing is modified in place; w is not kept; no dropout (inference).  Ua_all [n_rows, L, A], Vd_all
+ * [n_rows, L, F], offsets are 64-bit.  A row outside [0, n_rows) sets *oob_flag (may be NULL) and is never used as an address:
+ * its out row is zeros, its score act(0).  L <= 256, F <= 4096, F % 4 == 0, Ua_all / Vd_all / out 16-byte aligned.               */
+int ebn_pap_indexed_f32(const float* Ua_all, const float* Vd_all, int64_t n_rows, const int32_t* row_idx, const float* Q,
+                        const int32_t* q_idx, int64_t n_q, float* out, const float* users, float* scores, int32_t mode,
+                        int32_t* oob_flag, int64_t n_seq, int32_t L, int32_t F, int32_t A, ebn_stream_t stream);
+
 /* ---- top-N recommendation from an encoded catalogue (examples/beyond_accuracy/make_beyond_accuracy.ipynb, cell "Your Model":
  * every beyond-accuracy user's top-N out of one shared candidate list; scorers of nrms.py / nrms_docvec.py / lstur.py / naml.py:
  * act(user . news)) ---------------------------------------------------------------------------------------------------------------

@@ -1,22 +1,27 @@
 """Times scorer.predict over a synthetic eval-mode loader with the article catalogue encoded once against the per-batch path, for
-LSTUR (lstur-c1) or NAML (naml-c1), in ONE run on one GPU: the per-batch figure is the baseline of the cached figure beside it.
+LSTUR (lstur-c1), NAML (naml-c1) or NPA (npa-c1), in ONE run on one GPU: the per-batch figure is the baseline of the cached figure beside it.
 
 Loader (flags for its size): 20 000 articles, 100 000 impressions, in-view lengths 4 + geometric with mean about 11.6 and 0.2 % of
 the lists 250 long (the me-c1 distribution), H = 20 (left-padded histories of different lengths), batch 1024; 32000 x 300 word table.
 Model shapes: lstur-c1 (T 30, filter_num = gru_unit 400, window 3, attention_hidden_dim 200, n_users 50000, --type ini|con) and
-naml-c1 (T 30, body 40, 100 x 10 vert / subvert tables, filter_num 400, attention_hidden_dim 200).  Reported per run:
+naml-c1 (T 30, body 40, 100 x 10 vert / subvert tables, filter_num 400, attention_hidden_dim 200); npa-c1 (T 30, filter_num 400,
+window 3, attention_hidden_dim 200, user_emb_dim 400, n_users 50000) over the LSTUR leg's loader.  Reported per run:
   * impressions/s of scorer.predict with the cache and without it (wall clock around the call: loader slicing, uploads, launches,
     the download of every batch's scores), `--reps` rounds each, interleaved, after a warm-up of both paths on the first batches;
   * the catalogue build on its own (encode_catalogue, synchronised);
   * NAML: the indexed pooling-and-scoring kernel over the WHOLE loader in one launch (HIP events), as row-read bandwidth
     (history + candidate rows x F x 4 bytes / time) beside this box's float4-copy calibration measured in the same run (the
     library's gather kernel over the identity permutation of 4 KB rows, 1 GiB, (read + write bytes) / time);
-    LSTUR: the indexed GRU (H launches) of one full batch.
-Prints ONE JSON line; asserts that the two paths agree to 2e-6 and that the cached path is the faster one by more than 4 %.
+    LSTUR: the indexed GRU (H launches) of one full batch;
+    NPA: the indexed personalised pooling fused with the score over EVERY candidate of the loader in one launch, as catalogue-read
+    bandwidth (candidates x T x (F + A) x 4 bytes / time: the bytes it must read) beside the same float4-copy calibration, and the
+    catalogue's bytes.  The NPA result line is also appended to profiles/cached_scoring_npa_c1.jsonl (--out).
+Prints ONE JSON line; asserts that the two paths agree to 2e-6 and (LSTUR, NAML) that the cached path is the faster one by more
+than 4 %; for NPA the line carries "cached_is_faster" instead (the default of the cached path follows it).
 One model per process.  Run the two models as two steps, each under its own time limit, chained with && :
     timeout -k 10 900 python tools/cached_scoring_probe.py --model lstur && timeout -k 10 900 python tools/cached_scoring_probe.py --model naml
 Per-kernel times come from a separate run under `rocprofv3 --kernel-trace --stats -- python tools/cached_scoring_probe.py ...`.
-usage: cached_scoring_probe.py --model lstur|naml [--type ini|con] [--articles N] [--impressions N] [--history H] [--batch B] [--reps K]"""
+usage: cached_scoring_probe.py --model lstur|naml|npa [--out FILE] [--type ini|con] [--articles N] [--impressions N] [--history H] [--batch B] [--reps K]"""
 import argparse
 import ctypes
 import json
@@ -78,7 +83,7 @@ def make_frame(n_articles, n_impressions, H, seed=0, long_share=0.002):
 
 
 def build(a):
-    from ebrec.models.newsrec import LSTURModel, NAMLModel
+    from ebrec.models.newsrec import LSTURModel, NAMLModel, NPAModel
     from ebrec.models.newsrec.dataloader import LSTURDataLoader, NAMLDataLoader
 
     rng = np.random.default_rng(1)
@@ -99,6 +104,16 @@ def build(a):
         model = LSTURModel(hp, vocab_size=V, word_emb_dim=E, seed=1)
         with torch.no_grad():  # the user table is zeros at initialisation: give the "ini" GRU something to start from
             model._engine.user_table.uniform_(-0.1, 0.1)
+    elif a.model == "npa":
+        class hp:
+            title_size, history_size, n_users, cnn_activation = T, a.history, 50000, "relu"
+            attention_hidden_dim, user_emb_dim, filter_num, window_size = 200, 400, 400, 3
+            optimizer, loss, dropout, learning_rate = "adam", "cross_entropy_loss", 0.2, 1e-4
+
+        loader = LSTURDataLoader(user_id_mapping={u: u + 1 for u in range(50000)}, **common)
+        model = NPAModel(hp, vocab_size=V, word_emb_dim=E, seed=1)
+        with torch.no_grad():  # zeros at initialisation: every user would carry the same two queries
+            model._engine.user_table.uniform_(-0.5, 0.5)
     else:
         class hp:
             title_size, body_size, history_size = T, Tb, a.history
@@ -143,7 +158,8 @@ def timed_predict(model, loader, cache):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", required=True, choices=["lstur", "naml"])
+    ap.add_argument("--model", required=True, choices=["lstur", "naml", "npa"])
+    ap.add_argument("--out", default=None, help="file the result line is appended to (npa: profiles/cached_scoring_npa_c1.jsonl)")
     ap.add_argument("--type", default="ini", choices=["ini", "con"])
     ap.add_argument("--articles", type=int, default=20_000)
     ap.add_argument("--impressions", type=int, default=100_000)
@@ -198,6 +214,32 @@ def main():
                   "ms": round(ms, 4), "row_read_gbs": round(row_bytes / ms / 1e6, 1),
                   "row_read_of_float4_copy": round(row_bytes / ms / 1e6 / copy_gbs, 4),
                   "catalogue_mb": round(cache.n_rows * F * 4 / 1e6, 1)}
+    elif a.model == "npa":  # the candidate leg (pooling + score, nothing written but the scores) over the whole loader in one launch
+        T, A = hp.title_size, hp.attention_hidden_dim
+        parts, base = [], 0
+        for i in range(len(loader)):
+            user, _h, cand_idx, rows, _y = loader.user_index_eval_batch(i)
+            parts.append((np.asarray(cand_idx).reshape(-1), np.asarray(rows).reshape(-1) + base))
+            base += len(user)
+        cand = torch.from_numpy(np.concatenate([c for c, _ in parts]).astype(np.int32)).cuda()
+        imp = torch.from_numpy(np.concatenate([r for _, r in parts]).astype(np.int32)).cuda()
+        assert base == n_imp and cand.numel() == n_cand
+        Q = torch.empty(n_imp, A, device="cuda").uniform_(-1, 1)
+        users = torch.empty(n_imp, F, device="cuda").uniform_(-0.05, 0.05)
+        out = torch.empty(n_cand, device="cuda")
+        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+        fn = lambda: _hip.call("ebn_pap_indexed_f32", P(cache.Ua_all), P(cache.Vd_all), cache.n_rows, P(cand), P(Q), P(imp), n_imp, None,
+                               P(users), P(out), 1, P(flag), n_cand, T, F, A, S())
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        assert int(flag.item()) == 0
+        ms = sorted(events_ms(fn, 5) for _ in range(3))[1]
+        must_read = n_cand * T * (F + A) * 4
+        kernel = {"kernel": "ebn_pap_indexed_f32", "sequences": n_cand, "bytes_per_pair": T * (F + A) * 4, "ms": round(ms, 4),
+                  "catalogue_read_gbs": round(must_read / ms / 1e6, 1),
+                  "catalogue_read_of_float4_copy": round(must_read / ms / 1e6 / copy_gbs, 4),
+                  "catalogue_bytes": eng.catalogue_bytes(cache.n_rows), "catalogue_mb": round(eng.catalogue_bytes(cache.n_rows) / 1e6, 1)}
     else:  # the indexed GRU of one full batch
         user, his_idx, _c, _r, _y = loader.user_index_eval_batch(0)
         B, U = len(user), hp.gru_unit
@@ -221,9 +263,16 @@ def main():
            "cached_impressions_per_s": round(n_imp / best["cached"], 1), "per_batch_impressions_per_s": round(n_imp / best["per_batch"], 1),
            "speedup": round(best["per_batch"] / best["cached"], 2), "catalogue_build_s": round(t_build, 4),
            "max_abs_diff_cached_vs_per_batch": diff, "float4_copy_gbs": round(copy_gbs, 1), "hot_kernel": kernel}
+    if a.model == "npa":
+        res["cached_is_faster"] = bool(best["cached"] < best["per_batch"])
     print(json.dumps(res))
+    out_path = a.out or (str(ROOT / "profiles" / "cached_scoring_npa_c1.jsonl") if a.model == "npa" else None)
+    if out_path:
+        with open(out_path, "a") as fh:
+            fh.write(json.dumps(res) + "\n")
     assert diff <= 2e-6, f"cached and per-batch scores differ by {diff:.3e}"
-    assert best["per_batch"] / best["cached"] > 1.04, "the cached path is not faster than the per-batch path beyond the 4 % spread"
+    if a.model != "npa":
+        assert best["per_batch"] / best["cached"] > 1.04, "the cached path is not faster than the per-batch path beyond the 4 % spread"
 
 
 if __name__ == "__main__":
