@@ -3,3 +3,4 @@ from .metrics_protocols import (  # noqa: F401
 )
 from .beyond_accuracy import Coverage, Distribution, IntralistDiversity, Novelty, Serendipity  # noqa: F401
 from .device_metrics import DeviceMetricEvaluator, RaggedLists  # noqa: F401
+from .rerank import MMR, mmr_rerank  # noqa: F401

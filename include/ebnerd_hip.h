@@ -1003,6 +1003,25 @@ int ebn_topk_score_f32(const float* users, const float* news_all, int64_t n_rows
                        float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, int32_t F,
                        ebn_stream_t stream);
 
+/* ---- MMR re-ranking of a relevance pool (greedy Maximal Marginal Relevance over the distance of IntralistDiversity,
+ * beyond_accuracy.py:81-96: the list a top-N of ebn_topk_score_f32 with k = P becomes when relevance is traded against diversity) ---
+ * Per user u of U: P pool entries, relevance pool_rel[u, i] and row pool_rows[u, i] of the UNIT table unit [n_rows, D] (what
+ * ebn_ba_unit_rows_f32 leaves).  An entry is ABSENT when its row is outside [0, n_rows) (-1 is the padding of a short list and sets
+ * nothing, any other such row sets flags[0]) or its relevance is not finite (-inf is the padding, NaN and +inf set flags[1]); an
+ * absent entry's row is never turned into an address.  d(i, j) = fminf(fmaxf(1 - u_i . u_j, 0), 2), the dot product in exact fp32 (one
+ * MFMA fma chain over D in a fixed order); a NaN dot product between two present entries gives d = 0 and sets flags[1].
+ * Round 0 picks the present entry with the largest relevance (obj = rel); round t >= 1 picks, among the present entries not yet
+ * picked, the largest obj_i = lam * rel_i + (1 - lam) * min over picked j of d(i, j).  Larger obj first, equal obj to the smaller pool
+ * index.  The rounds end after k picks or when nothing is left; lam = 1 gives the relevance order of the pool, which need not
+ * arrive sorted.  out_sel [U, k]: the pool INDEX of each pick, -1 in the empty trailing slots; out_obj [U, k] (may be NULL): its
+ * objective, -inf in empty slots.  flags [2] is only ever SET (the caller zeroes it and may let it accumulate over calls).
+ * Limits: 1 <= P <= 64, 1 <= k <= 64 (k > P is legal: the lists come back short), D % 4 == 0, 4 <= D <= 8192 (EBN_ERR_UNSUPPORTED);
+ * lam outside [0, 1] or NaN: EBN_ERR_BAD_ARG; unit 16-byte aligned (EBN_ERR_ALIGN).  U == 0: nothing to do.  A failing call writes
+ * nothing.  One workgroup per user (two users when P <= 32), no atomics: a user's output bits depend neither on U nor on the users
+ * that share its launch, and two runs give the same bits.                                                                       */
+int ebn_mmr_rerank_f32(const float* unit, int64_t n_rows, int32_t D, const int32_t* pool_rows, const float* pool_rel, int32_t P,
+                       int32_t k, float lam, int32_t* out_sel, float* out_obj, int32_t* flags, int64_t U, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
