@@ -1,5 +1,6 @@
 """Beyond-accuracy evaluation (reference: evaluation/beyond_accuracy.py): IntralistDiversity, Distribution, Coverage,
-Sentiment, Serendipity, Novelty -- same names, call signatures and return types.
+Sentiment, Serendipity, Novelty -- same names, call signatures and return types -- and Calibration, the KL divergence between a
+user's click history and a list over a label attribute (what ebrec.evaluation.rerank.Calibrated optimises).
 
 Two paths.  With a plain dict as `lookup_dict` everything runs on the host in float64 numpy, list by list, as the reference
 does.  With a `DeviceLookup` (a read-only Mapping over the same dict that also keeps its vector / scalar columns on the GPU),
@@ -36,13 +37,18 @@ class DeviceLookup(Mapping):
     float32 array.  The tables are uploaded at the first device call; vector tables are normalised to unit rows there
     (ebn_ba_unit_rows_f32).  `device=None` keeps everything on the host: the classes then take their host path.
 
+    Per key of `label_keys` -- a categorical attribute such as `category` (one label) or `topics` (a list of labels) -- it holds
+    the sorted distinct labels (`label_vocabulary`) and the label table W [n_items, C] float32: a one-hot row for a single label,
+    1 / n on each of the n distinct labels of a list, a zero row for `None` or an empty list.  It is uploaded as it is.
+
     The ids must be sortable against each other (all strings or all integers)."""
 
-    def __init__(self, lookup_dict: dict, vector_keys: Iterable[str] = (), scalar_keys: Iterable[str] = (), device="cuda"):
+    def __init__(self, lookup_dict: dict, vector_keys: Iterable[str] = (), scalar_keys: Iterable[str] = (), device="cuda", *,
+                 label_keys: Iterable[str] = ()):
         self._dict = lookup_dict
-        self.vector_keys, self.scalar_keys = tuple(vector_keys), tuple(scalar_keys)
+        self.vector_keys, self.scalar_keys, self.label_keys = tuple(vector_keys), tuple(scalar_keys), tuple(label_keys)
         self.device = device
-        for key in self.vector_keys + self.scalar_keys:
+        for key in self.vector_keys + self.scalar_keys + self.label_keys:
             check_key_in_all_nested_dicts(lookup_dict, key)
         keys = np.asarray(list(lookup_dict))
         if keys.dtype.kind not in "iuUS" and len(keys):
@@ -51,7 +57,7 @@ class DeviceLookup(Mapping):
         self.ids = keys[order]
         self._key_list = [k for k in lookup_dict]
         self._order = order
-        self._host, self._dev = {}, {}
+        self._host, self._dev, self._labels = {}, {}, {}
 
     # ---- Mapping ----
     def __getitem__(self, key):
@@ -68,10 +74,32 @@ class DeviceLookup(Mapping):
 
     # ---- host side of the device path ----
     def holds(self, key: str) -> bool:
-        return self.device is not None and (key in self.vector_keys or key in self.scalar_keys)
+        return self.device is not None and (key in self.vector_keys or key in self.scalar_keys or key in self.label_keys)
+
+    def _label_table(self, key: str):
+        """(vocabulary, W [n_items, C] float64) of a label key, built once"""
+        if key not in self._labels:
+            if key not in self.label_keys:
+                raise KeyError(key)
+            per_item = [distinct_labels(self._dict[self._key_list[i]][key]) for i in self._order]
+            vocab = sorted(set(chain.from_iterable(per_item)))
+            column = {label: c for c, label in enumerate(vocab)}
+            W = np.zeros((len(per_item), len(vocab)))
+            for r, labels in enumerate(per_item):
+                for label in labels:
+                    W[r, column[label]] = 1.0 / len(labels)
+            self._labels[key] = (vocab, W)
+        return self._labels[key]
+
+    def label_vocabulary(self, key: str) -> list:
+        """The sorted distinct labels of a label key: column c of its table belongs to label_vocabulary(key)[c]."""
+        return list(self._label_table(key)[0])
 
     def host_table(self, key: str) -> np.ndarray:
-        """float32 column `key` in row order: [n_items, D] for a vector key (as stored, NOT normalised), [n_items] for a scalar key."""
+        """float32 column `key` in row order: [n_items, D] for a vector key (as stored, NOT normalised), [n_items] for a scalar
+        key, the label table [n_items, C] for a label key."""
+        if key not in self._host and key in self.label_keys:
+            self._host[key] = self._label_table(key)[1].astype(np.float32)
         if key not in self._host:
             if key not in self.vector_keys and key not in self.scalar_keys:
                 raise KeyError(key)
@@ -111,7 +139,8 @@ class DeviceLookup(Mapping):
 
     # ---- device side ----
     def device_table(self, key: str):
-        """The uploaded column: unit rows [n_items, D] for a vector key, values [n_items] for a scalar key (torch tensors)."""
+        """The uploaded column: unit rows [n_items, D] for a vector key, values [n_items] for a scalar key, the label table
+        [n_items, C] as it is for a label key (torch tensors)."""
         if key not in self._dev:
             import torch
 
@@ -124,6 +153,26 @@ class DeviceLookup(Mapping):
                     _hip.call("ebn_ba_unit_rows_f32", _hip.ptr(t), _hip.ptr(t), t.shape[0], t.shape[1], _hip.stream_handle())
             self._dev[key] = t
         return self._dev[key]
+
+
+def distinct_labels(value) -> list:
+    """The distinct labels of one item's attribute, in order of first appearance: [] for None, the elements of a list / tuple /
+    set / array (None among them dropped), otherwise the value itself as the only label."""
+    if value is None:
+        return []
+    if isinstance(value, (list, tuple, set, frozenset, np.ndarray)):
+        return list(dict.fromkeys(v.item() if isinstance(v, np.generic) else v for v in value if v is not None))
+    return [value.item() if isinstance(value, np.generic) else value]
+
+
+def label_lookup(lookup_dict, lookup_key: str) -> DeviceLookup:
+    """`lookup_dict` itself when it is a DeviceLookup with `lookup_key` among its label keys, else a host-only one over the same
+    items: ONE rule for the vocabulary and the label table, whichever path uses them."""
+    if isinstance(lookup_dict, DeviceLookup):
+        if lookup_key in lookup_dict.label_keys:
+            return lookup_dict
+        lookup_dict = lookup_dict._dict
+    return DeviceLookup(lookup_dict, label_keys=(lookup_key,), device=None)
 
 
 def _on_device(lookup_dict, lookup_key, pairwise_distance_function=cosine_distances) -> bool:
@@ -412,3 +461,45 @@ class Novelty:
         R = get_keys_in_dict(R, lookup_dict)
         popularity_scores = sorted([lookup_dict[id_].get(lookup_key) for id_ in R])
         return novelty(popularity_scores[-n_recommendations:]), novelty(popularity_scores[:n_recommendations])
+
+
+### Calibration
+class Calibration:
+    """KL(p || q~) between each user's click history and recommendation list over a label attribute (Steck, RecSys 2018): p is
+    the mean label row of the history, q the mean label row of the list, q~ = (1 - alpha) q + alpha p.  An item's label row is
+    one-hot for a single label, 1 / n on each of the n distinct labels of a list, zeros for None.  Ids that are not keys of
+    `lookup_dict` are dropped; a history left empty gives 0 (nothing to be calibrated to), a list left empty NaN.
+
+    >>> lookup_dict = {"item1": {"g": "Action"}, "item2": {"g": "Action"}, "item3": {"g": "Comedy"}, "item4": {"g": None}}
+    >>> R = [np.array(["item1", "item3"]), np.array(["item1", "item2"]), np.array(["item3", "item4"])]
+    >>> H = [np.array(["item1", "item3"]), np.array(["item1", "item3"]), np.array(["itemX"])]
+    >>> Calibration()(R, H, lookup_dict, "g")
+    array([0.        , 1.95851777, 0.        ])
+    """
+
+    def __init__(self) -> None:
+        self.name = "calibration"
+
+    def __call__(self, R, H, lookup_dict, lookup_key: str, alpha: float = 0.01) -> np.ndarray:
+        if len(R) != len(H):
+            raise ValueError(f"The lengths of 'R' and 'H' do not match ({len(R)} != {len(H)}).")
+        if not 0.0 < float(alpha) < 1.0:
+            raise ValueError(f"alpha must lie in (0, 1), got {alpha}")
+        lookup = label_lookup(lookup_dict, lookup_key)
+        W = lookup._label_table(lookup_key)[1]
+
+        def mean_rows(lists):  # [n, C] mean label row of the valid ids of each list, and their number [n]
+            rows, off = lookup.map_lists(lists if isinstance(lists, np.ndarray) else [np.asarray(x) for x in lists])
+            owner = np.repeat(np.arange(len(off) - 1), np.diff(off))
+            ok = rows >= 0
+            total = np.zeros((len(off) - 1, W.shape[1]))
+            np.add.at(total, owner[ok], W[rows[ok]])
+            count = np.bincount(owner[ok], minlength=len(off) - 1)
+            return total / np.maximum(count, 1)[:, None], count
+
+        p, _ = mean_rows(H)
+        q, n_r = mean_rows(R)
+        q = (1.0 - alpha) * q + alpha * p
+        with np.errstate(divide="ignore", invalid="ignore"):
+            kl = np.where(p > 0, p * np.log(p / q), 0.0).sum(1)
+        return np.where(n_r > 0, kl, np.nan)

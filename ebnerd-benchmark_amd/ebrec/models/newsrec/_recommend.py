@@ -16,6 +16,10 @@ All cacheable models score as act(user . news): the catalogue is encoded once, a
 ``rerank=MMR(lookup, key, lam, pool)`` (ebrec/evaluation/rerank.py) diversifies the lists: the same launch keeps each user's best
 ``pool``, their positions are mapped to rows of the lookup's unit table on the device, and ``ebn_mmr_rerank_f32`` picks ``top_n`` of
 them greedily by lam * score + (1 - lam) * (distance to the nearest item already picked).
+``rerank=Calibrated(lookup, key, lam, pool, alpha, target, history_weights)`` calibrates them instead: the pool is formed the same
+way, ``ebn_label_target_f32`` turns the batch's history rows (mapped to the lookup's rows through one host-built int32 map) into
+each user's target label distribution, and ``ebn_calibrated_rerank_f32`` picks ``top_n`` greedily by
+lam * score - (1 - lam) * KL(target || the list's label distribution).
 """
 from __future__ import annotations
 
@@ -23,7 +27,10 @@ import numpy as np
 import torch
 
 from ebrec import _hip
-from ebrec.evaluation.rerank import MAX_POOL, MMR, check_lam, mmr_select
+from ebrec.evaluation.rerank import (
+    MAX_HISTORY, MAX_LABELS, MAX_POOL, MMR, Calibrated, calibrated_select, check_alpha, check_history_weights, check_lam,
+    given_target, label_target, mmr_select,
+)
 
 MAX_TOP_N, MAX_EXCLUDE = 64, 256  # limits of ebn_topk_score_f32 (include/ebnerd_hip.h)
 
@@ -60,13 +67,15 @@ def _check(model, loader, top_n, scores):
 def _check_rerank(rerank, top_n, cand_ids):
     """Host side of ``rerank=``: -> (pool, lookup rows [M] int32 of the candidates).  Everything that can be wrong with the
     arguments is found here, before the device works."""
-    if not isinstance(rerank, MMR):
-        raise ValueError(f"rerank must be None or an MMR(lookup, key, lam, pool), got {type(rerank).__name__}")
+    if not isinstance(rerank, (MMR, Calibrated)):
+        raise ValueError(f"rerank must be None or an MMR(lookup, key, lam, pool) or a Calibrated(lookup, key, ...), got {type(rerank).__name__}")
     check_lam(rerank.lam)
     pool = int(rerank.pool)
     if not top_n <= pool <= MAX_POOL:
-        raise ValueError(f"the MMR pool must lie in [top_n, {MAX_POOL}] = [{top_n}, {MAX_POOL}], got {pool}")
+        raise ValueError(f"the {type(rerank).__name__} pool must lie in [top_n, {MAX_POOL}] = [{top_n}, {MAX_POOL}], got {pool}")
     lookup, key = rerank.lookup, rerank.key
+    if isinstance(rerank, Calibrated):
+        return min(pool, len(cand_ids)), _check_calibrated(rerank, cand_ids)
     if not (hasattr(lookup, "holds") and lookup.holds(key) and key in lookup.vector_keys):
         raise ValueError(f"MMR needs a DeviceLookup that holds '{key}' as a vector key")
     rows = lookup.rows_of(cand_ids)
@@ -78,6 +87,41 @@ def _check_rerank(rerank, top_n, cand_ids):
     if D == 0 or D % 4:
         raise ValueError(f"MMR needs a vector width that is a positive multiple of 4, '{key}' has {D}")
     return min(pool, len(rows)), rows
+
+
+def _check_calibrated(rerank: Calibrated, cand_ids):
+    """-> lookup rows [M] int32 of the candidates; the rest of what can be wrong with a Calibrated(...)"""
+    lookup, key = rerank.lookup, rerank.key
+    check_alpha(rerank.alpha)
+    if not (hasattr(lookup, "holds") and lookup.holds(key) and key in lookup.label_keys):
+        raise ValueError(f"Calibrated needs a DeviceLookup that holds '{key}' as a label key")
+    C = len(lookup.label_vocabulary(key))
+    if not 1 <= C <= MAX_LABELS:
+        raise ValueError(f"Calibrated supports 1 to {MAX_LABELS} labels, '{key}' has {C}")
+    if isinstance(rerank.target, str):
+        if rerank.target != "history":
+            raise ValueError(f"the Calibrated target must be 'history', a {{label: weight}} dict or a [C] array, got {rerank.target!r}")
+        check_history_weights(rerank.history_weights)
+    elif given_target(rerank.target, lookup.label_vocabulary(key)).ndim != 1:
+        raise ValueError("a given Calibrated target is ONE distribution for every impression: a {label: weight} dict or a [C] array")
+    rows = lookup.rows_of(cand_ids)
+    if (rows < 0).any():
+        missing = list(dict.fromkeys(np.asarray(cand_ids)[rows < 0].tolist()))
+        more = f" and {len(missing) - 5} more" if len(missing) > 5 else ""
+        raise ValueError(f"candidate ids without a '{key}' label row in the Calibrated lookup: {missing[:5]}{more}")
+    return rows
+
+
+def _history_row_map(row_of_id: dict, lookup, n_news_rows: int) -> np.ndarray:
+    """[n_news_rows] int32: row of the encoded catalogue -> row of the lookup's tables, -1 for the padding row 0, for rows no
+    article id points at and for articles the lookup lacks"""
+    out = np.full(n_news_rows, -1, np.int32)
+    if row_of_id:
+        ids = np.asarray(list(row_of_id))
+        rows = np.fromiter(row_of_id.values(), dtype=np.int64, count=len(row_of_id))
+        keep = (rows > 0) & (rows < n_news_rows)
+        out[rows[keep]] = lookup.rows_of(ids[keep])
+    return out
 
 
 def topk(users: torch.Tensor, news_all: torch.Tensor, cand_rows, exclude, k: int, sigmoid: bool, flags: torch.Tensor, n_splits: int = 0):
@@ -109,10 +153,16 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     ``rerank=MMR(lookup, key, lam=0.7, pool=50)``: each list is the greedy MMR order of the impression's ``pool`` best candidates
     (``pool`` in [top_n, 64], clamped to the number of candidates; every candidate id must have a ``key`` vector in ``lookup``)
     with the score chosen by ``scores`` as the relevance; ``lam = 1`` gives the plain lists.  The returned scores are then still
-    the MODEL's score of each kept item, in selection order: they are NOT monotone along a list."""
+    the MODEL's score of each kept item, in selection order: they are NOT monotone along a list.
+    ``rerank=Calibrated(lookup, key, lam=0.7, pool=50, alpha=0.01, target="history", history_weights=None)``: each list is the
+    greedy calibrated order of the same pool (ebrec/evaluation/rerank.py): lam * score - (1 - lam) * KL(target || list) over the
+    labels ``lookup`` holds under the label key ``key``.  The target is the label distribution of the impression's own history --
+    needed even with ``exclude_history=False``; ``history_weights`` [H] weighs the loader's history slots -- or one given
+    {label: weight} dict / [C] array for everybody.  Scores as for MMR."""
     _check(model, loader, top_n, scores)
     top_n = int(top_n)
-    cand_ids, rows = candidate_rows(model._recommend_index(loader), candidate_ids)
+    index = model._recommend_index(loader)
+    cand_ids, rows = candidate_rows(index, candidate_ids)
     if top_n > len(rows):
         raise ValueError(f"top_n = {top_n} is larger than the number of candidates ({len(rows)})")
     if rerank is not None:
@@ -122,9 +172,17 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     device = news_all.device
     cand_d = torch.from_numpy(rows).to(device)
     flags = torch.zeros(2, dtype=torch.int32, device=device)
+    calibrated = isinstance(rerank, Calibrated)
+    from_history = calibrated and isinstance(rerank.target, str)
     if rerank is not None:
-        unit = rerank.lookup.device_table(rerank.key)
+        unit = rerank.lookup.device_table(rerank.key).to(device)  # MMR: the unit rows; Calibrated: the label table
         row_of_pos = torch.from_numpy(lookup_rows).to(device)  # candidate position -> row of the lookup's table
+    if from_history:
+        lookup_row_of_news = torch.from_numpy(_history_row_map(index, rerank.lookup, news_all.shape[0])).to(device)
+        slot_w = check_history_weights(rerank.history_weights)
+    elif calibrated:
+        shared = torch.from_numpy(given_target(rerank.target, rerank.lookup.label_vocabulary(rerank.key)).astype(np.float32)).to(device)
+    need_his = exclude_history or from_history
     pos_out, score_out, users, his, pending = [], [], [], [], 0
 
     def flush():
@@ -132,13 +190,25 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
         if not users:
             return
         u = torch.cat(users).contiguous()
-        ex = torch.cat(his).contiguous() if exclude_history else None
+        hh = torch.cat(his).contiguous() if need_his else None
+        ex = hh if exclude_history else None
         if rerank is None:
             p, s = topk(u, news_all, cand_d, ex, top_n, scores == "sigmoid", flags)
         else:  # the pool, its rows in the lookup's table (-1 stays -1), the greedy picks, and the picks' positions and scores
             pp, ps = topk(u, news_all, cand_d, ex, pool, scores == "sigmoid", flags)
             pool_rows = torch.where(pp >= 0, row_of_pos[pp.clamp(min=0).long()], pp).contiguous()
-            sel, _ = mmr_select(unit.to(device), pool_rows, ps, top_n, rerank.lam, flags)
+            if not calibrated:
+                sel, _ = mmr_select(unit, pool_rows, ps, top_n, rerank.lam, flags)
+            else:
+                if from_history:  # history rows of the catalogue -> rows of the label table (outside the catalogue: the padding)
+                    inside = (hh >= 0) & (hh < lookup_row_of_news.shape[0])
+                    hist_rows = torch.where(inside, lookup_row_of_news[hh.clamp(0, lookup_row_of_news.shape[0] - 1).long()],
+                                            torch.full_like(hh, -1)).contiguous()
+                    w = None if slot_w is None else torch.from_numpy(slot_w.astype(np.float32)).to(device)
+                    target = label_target(unit, hist_rows, w, flags)
+                else:
+                    target = shared
+                sel, _ = calibrated_select(unit, pool_rows, ps, target, top_n, rerank.lam, rerank.alpha, flags)
             kept = sel.clamp(min=0).long()
             p = torch.where(sel >= 0, pp.gather(1, kept), sel)
             s = torch.where(sel >= 0, ps.gather(1, kept), torch.full_like(ps[:, :1], float("-inf")))
@@ -150,10 +220,14 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
 
     for i in range(len(loader)):
         user, his_rows = model._user_vectors_cached(cache, loader, i)
-        if exclude_history:
+        if need_his:
             h = torch.as_tensor(np.ascontiguousarray(his_rows, dtype=np.int32)).to(device)
-            if h.shape[1] > MAX_EXCLUDE:
+            if exclude_history and h.shape[1] > MAX_EXCLUDE:
                 raise ValueError(f"exclude_history supports histories of at most {MAX_EXCLUDE} articles, got {h.shape[1]}")
+            if from_history and not 1 <= h.shape[1] <= MAX_HISTORY:
+                raise ValueError(f"a history target supports histories of 1 to {MAX_HISTORY} articles, got {h.shape[1]}")
+            if from_history and slot_w is not None and len(slot_w) != h.shape[1]:
+                raise ValueError(f"history_weights has {len(slot_w)} entries, the loader's histories {h.shape[1]} slots")
             if his and his[0].shape[1] != h.shape[1]:
                 flush()
             his.append(h)

@@ -1022,6 +1022,45 @@ int ebn_topk_score_f32(const float* users, const float* news_all, int64_t n_rows
 int ebn_mmr_rerank_f32(const float* unit, int64_t n_rows, int32_t D, const int32_t* pool_rows, const float* pool_rel, int32_t P,
                        int32_t k, float lam, int32_t* out_sel, float* out_obj, int32_t* flags, int64_t U, ebn_stream_t stream);
 
+/* ---- calibrated re-ranking of a relevance pool (Steck, RecSys 2018: the greedy list whose label distribution stays close, in KL
+ * divergence, to a target distribution -- what Distribution, beyond_accuracy.py:158-209, reports over category / sentiment_label /
+ * topics in examples/beyond_accuracy/make_beyond_accuracy.ipynb) -----------------------------------------------------------------
+ * LABEL TABLE W [n_rows, C] float32, one row per article: W[r, c] >= 0 is the share of label c in article r -- a one-hot row for a
+ * single-valued attribute, 1 / len on each distinct label of a list-valued one, a zero row for no label (a legal pick that only
+ * dilutes the list).
+ *
+ * ebn_label_target_f32: the history target.  hist_rows [U, H] rows of W, hist_w [H] one weight per history SLOT (decay weights) or
+ * NULL = all ones.  target[u, c] = sum_h w_h W[hist_rows[u, h], c] / sum_h w_h over the slots whose row lies in [0, n_rows), each
+ * label summed in slot order; a row of -1 is the padding and sets nothing, any other row outside the table sets flags[0]; such a
+ * row is never turned into an address.  No valid slot, or a weight sum that is not > 0, gives a zero row.  target [U, C] is
+ * written whole.  Limits: 1 <= C <= 128, 1 <= H <= 256 -- the X limit of ebn_topk_score_f32, so a caller can pass the history it
+ * excludes by (EBN_ERR_UNSUPPORTED); U or n_rows outside [0, 2^31 - 1]: EBN_ERR_BAD_ARG.  U == 0: nothing to do.  A failing call
+ * writes nothing.  flags [2] is only ever SET.  One wave per user, no atomics.                                                    */
+int ebn_label_target_f32(const float* W, int64_t n_rows, int32_t C, const int32_t* hist_rows, int32_t H, const float* hist_w,
+                         float* target, int32_t* flags, int64_t U, ebn_stream_t stream);
+/* ebn_calibrated_rerank_f32.  Per user u of U: P pool entries, relevance pool_rel[u, i] and row pool_rows[u, i] of W, under the
+ * contract of ebn_mmr_rerank_f32: an entry is ABSENT when its row is outside [0, n_rows) (-1 is the padding and sets nothing, any
+ * other such row sets flags[0]) or its relevance is not finite (-inf is the padding, NaN and +inf set flags[1]); an absent entry's
+ * row is never turned into an address.  The target p is target[u * target_stride + c]: target_stride = C gives a row per user,
+ * 0 ONE row for all users.  A target entry that is negative or not finite counts as 0 and sets flags[1]; the target is used as
+ * given, NOT renormalised; an all-zero target (an empty history) makes the calibration term 0 for every entry.
+ * After the picks I, with S_c = sum over j in I of W[row_j, c], n = |I|, q~_c = (1 - alpha) S_c / n + alpha p_c and
+ * KL(I) = sum over c with p_c > 0 of p_c logf(p_c / q~_c), EVERY round (round 0 too, unlike MMR) picks, among the present entries
+ * not yet picked, the largest obj_i = lam * rel_i - (1 - lam) * KL(I + {i}).  Larger obj first, equal obj to the smaller pool index;
+ * two entries with the same label row get the same KL bits.  The rounds end after k picks or when nothing is left; lam = 1 gives
+ * the relevance order of the pool (which need not arrive sorted) with out_obj = rel.  out_sel [U, k]: the pool INDEX of each pick,
+ * -1 in the empty trailing slots; out_obj [U, k] (may be NULL): its objective, -inf in empty slots.  flags [2] is only ever SET
+ * (the caller zeroes it and may let it accumulate over calls).
+ * Limits: 1 <= P <= 64, 1 <= k <= 64 (k > P is legal: the lists come back short), 1 <= C <= 128 (EBN_ERR_UNSUPPORTED).  Why 128:
+ * a user's label rows stay in LDS for all k rounds, and with P = 64 they are 64 x 129 floats = 32 KiB of the CU's 160 KiB --
+ * four users per CU; a wider label set would leave a CU to fewer waves than it has SIMDs.  lam outside [0, 1], alpha outside
+ * (0, 1), NaN in either, target_stride not in {0, C}, U or n_rows outside [0, 2^31 - 1]: EBN_ERR_BAD_ARG.  U == 0: nothing to do.
+ * A failing call writes nothing.  One wave per user, no atomics: a user's output bits depend neither on U nor on the users that
+ * share its launch, and two runs give the same bits.                                                                            */
+int ebn_calibrated_rerank_f32(const float* W, int64_t n_rows, int32_t C, const int32_t* pool_rows, const float* pool_rel, int32_t P,
+                              const float* target, int64_t target_stride, int32_t k, float lam, float alpha, int32_t* out_sel,
+                              float* out_obj, int32_t* flags, int64_t U, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
