@@ -20,68 +20,44 @@
 // survivors arrive, nor on how the candidates are split over workgroups: every element's dot product is the same fma chain whatever
 // the split, partial lists are merged in the same order by a second launch.  Bit-identical for every n_splits and from run to run.
 // Ranking is on the raw dot product; the sigmoid is applied to the k kept values when they are written.
-#include <math.h>
-
-#include "ebn_common.h"
+// The list code (LDS plan, drain and insert, write-out, merge and fill launches) is ebn_topk_list.h, shared with ebn_npa_topk.hip.
+#include "ebn_topk_list.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int TK_BM = 128, TK_BN = 128, TK_BK = 16, TK_THREADS = 256;
 constexpr int TK_TN = TK_BN / 32;      // MFMA tiles of a wave along the candidates
-constexpr int TK_QCAP = 2 * TK_BN;     // survivors of one accumulator index: 2 rows x 128 columns
-constexpr int TK_MAX_K = 64, TK_MAX_X = 256, TK_MAX_F = 8192, TK_MAX_SPLITS = 64;
-constexpr int TK_EMPTY = INT32_MAX;    // position of an empty slot inside the kernels (sorts after every real candidate)
-constexpr int TK_TILE_FLOATS = TK_BM * TK_BK;  // one operand slab image
+constexpr int TK_MAX_F = 8192;
+static_assert(TK_QCAP >= 2 * TK_BN, "the survivors of one accumulator index: 2 rows x 128 columns");
 
-struct TopkArgs {
+struct TopkArgs : TopkList {
   const float* users;
   const float* news;
   const int32_t* cand_rows;
-  const int32_t* exclude;
-  int32_t* out_pos;
-  float* out_score;
-  int32_t* flags;
-  int32_t* part_pos;   // [n_splits, U, k] (n_splits > 1)
-  float* part_score;
-  int64_t U, M, n_rows;
-  int32_t F, X, k, mode, n_splits, tiles_per_split;
+  int64_t M, n_rows;
+  int32_t F, tiles_per_split;
 };
 
-__device__ __forceinline__ float topk_act(float s, int mode) { return mode == 1 ? 1.0f / (1.0f + expf(-s)) : s; }
-
-// (s0, p0) ranks strictly before (s1, p1)
-__device__ __forceinline__ bool topk_before(float s0, int p0, float s1, int p1) { return s0 > s1 || (s0 == s1 && p0 < p1); }
-
-// dynamic LDS layout (floats): operand images | thr[128] | candrow[128] | queue score[4][256] | queue rowcol[4][256] | list score
-// [128][k] | list pos [128][k]
+// dynamic LDS layout: ebn_topk_list.h
 __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                           // 2 buffers
-  float* Bs = smem + 2 * TK_TILE_FLOATS;      // 2 buffers
-  volatile float* thr = smem + 4 * TK_TILE_FLOATS;
-  volatile int* candrow = reinterpret_cast<volatile int*>(smem + 4 * TK_TILE_FLOATS + TK_BM);
-  volatile float* qs_all = smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN;
-  volatile int* qrc_all = reinterpret_cast<volatile int*>(smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN + 4 * TK_QCAP);
-  volatile float* lsc = smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN + 8 * TK_QCAP;
-  volatile int* lps = reinterpret_cast<volatile int*>(smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN + 8 * TK_QCAP + TK_BM * a.k);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kl = lane >> 5, il = lane & 31;
-  const int k = a.k, F = a.F, X = a.X;
+  const int k = a.k, F = a.F;
   const int64_t u0 = static_cast<int64_t>(blockIdx.x) * TK_BM;
   const int split = blockIdx.y;
-  volatile float* qs = qs_all + wave * TK_QCAP;
-  volatile int* qrc = qrc_all + wave * TK_QCAP;
+  const TopkLds lds = topk_lds(smem, wave, k);
+  float *As = lds.As, *Bs = lds.Bs;
+  volatile float* thr = lds.thr;
+  volatile int* candrow = lds.candrow;
+  volatile float* qs = lds.qs;
+  volatile int* qrc = lds.qrc;
 
-  for (int i = tid; i < TK_BM * k; i += TK_THREADS) {
-    lsc[i] = -INFINITY;
-    lps[i] = TK_EMPTY;
-  }
-  if (tid < TK_BM) thr[tid] = -INFINITY;
+  topk_list_init(lds, k, tid);
   __syncthreads();  // a range without tiles (more splits than tiles divide into) still writes its empty lists out
 
   // this thread's two float4 of an operand slab: item v = tid + 256 i -> tile row v / 4, k quarter v % 4
@@ -222,117 +198,12 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
         }
         cnt += __popcll(m);
       }
-      for (int base = 0; base < cnt; base += 64) {
-        const int idx = base + lane;
-        bool ok = idx < cnt;
-        const float s = ok ? qs[idx] : 0.f;
-        const int rc = ok ? qrc[idx] : 0;
-        const int erl = rc >> 8, ecol = rc & 255;
-        const int64_t u = u0 + erl, c = n0 + ecol;
-        const int crow = candrow[ecol];
-        ok = ok && u < a.U && crow >= 0;
-        if (ok && s != s) {
-          saw_nan = true;
-          ok = false;
-        }
-        ok = ok && !(s < thr[erl]);
-        if (ok && X > 0) {
-          const int32_t* ex = a.exclude + u * X;
-          bool hit = false;
-          for (int x = 0; x < X; ++x) hit |= ex[x] == crow;
-          ok = !hit;
-        }
-        unsigned long long m = __ballot(ok);
-        while (m != 0ull) {
-          const int l = __builtin_ctzll(m);
-          m &= m - 1ull;
-          const float ns = __shfl(s, l, 64);
-          const int nrl = __shfl(erl, l, 64);
-          const int np = static_cast<int>(__shfl(static_cast<int>(c), l, 64));
-          // the whole wave inserts (ns, np) into the list of row nrl: lane t holds slot t
-          const bool in = lane < k;
-          const float es = in ? lsc[nrl * k + lane] : 0.f;
-          const int ep = in ? lps[nrl * k + lane] : 0;
-          const int rank = __popcll(__ballot(in && topk_before(es, ep, ns, np)));
-          const float us = __shfl_up(es, 1, 64);
-          const int up = __shfl_up(ep, 1, 64);
-          if (rank < k) {
-            if (in && lane >= rank) {
-              const float ws = lane == rank ? ns : us;
-              lsc[nrl * k + lane] = ws;
-              lps[nrl * k + lane] = lane == rank ? np : up;
-              if (lane == k - 1) thr[nrl] = ws;
-            }
-          }
-        }
-      }
+      topk_list_drain(a, lds, cnt, u0, n0, lane, saw_nan);
     }
   }
 
   if (saw_nan) a.flags[1] = 1;
-  // a wave writes the lists of its own 32 rows: lane t slot t
-  const bool direct = a.n_splits == 1;
-  for (int rr = 0; rr < 32; ++rr) {
-    const int rl = wave * 32 + rr;
-    const int64_t u = u0 + rl;
-    if (u >= a.U || lane >= k) continue;
-    const float es = lsc[rl * k + lane];
-    const int ep = lps[rl * k + lane];
-    if (direct) {
-      const bool empty = ep == TK_EMPTY;
-      a.out_pos[u * k + lane] = empty ? -1 : ep;
-      a.out_score[u * k + lane] = empty ? -INFINITY : topk_act(es, a.mode);
-    } else {
-      const int64_t o = (static_cast<int64_t>(split) * a.U + u) * k + lane;
-      a.part_pos[o] = ep;
-      a.part_score[o] = es;
-    }
-  }
-}
-
-// Merge of the n_splits (<= 64) sorted partial lists of a user: one wave per user, lane s holds the head of split s, k rounds of a
-// wave-wide "first in the total order".  Positions of real candidates are distinct, so the winner is unique.
-__global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t u = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (u >= a.U) return;
-  const int k = a.k;
-  const bool has = lane < a.n_splits;
-  const int64_t base = (static_cast<int64_t>(has ? lane : 0) * a.U + u) * k;
-  int head = 0;
-  for (int t = 0; t < k; ++t) {
-    const bool live = has && head < k;
-    const float s = live ? a.part_score[base + head] : -INFINITY;
-    const int p = live ? a.part_pos[base + head] : TK_EMPTY;
-    float bs = s;
-    int bp = p;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float os = __shfl_xor(bs, off, 64);
-      const int op = __shfl_xor(bp, off, 64);
-      if (topk_before(os, op, bs, bp)) {
-        bs = os;
-        bp = op;
-      }
-    }
-    const bool empty = bp == TK_EMPTY;
-    if (!empty && live && p == bp) ++head;
-    if (lane == 0) {
-      a.out_pos[u * k + t] = empty ? -1 : bp;
-      a.out_score[u * k + t] = empty ? -INFINITY : topk_act(bs, a.mode);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void topk_fill_empty_kernel(int32_t* __restrict__ out_pos, float* __restrict__ out_score, int64_t n) {
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
-    out_pos[i] = -1;
-    out_score[i] = -INFINITY;
-  }
-}
-
-int64_t topk_lds_bytes(int k) {
-  return static_cast<int64_t>(4 * TK_TILE_FLOATS + TK_BM + TK_BN + 8 * TK_QCAP + 2 * TK_BM * k) * 4;
+  topk_list_write(a, lds, u0, split, wave, lane);
 }
 
 int topk_resolve_splits(int64_t U, int64_t M, int32_t n_splits) {
@@ -373,13 +244,7 @@ extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int
   if (U == 0) return EBN_OK;
   EBN_REQUIRE(out_pos != nullptr && out_score != nullptr && flags != nullptr, EBN_ERR_BAD_ARG);
   hipStream_t s = ebn_stream(stream);
-  if (M == 0) {
-    const int64_t n = U * k;
-    const int64_t blocks = ebn_ceil_div(n, 256);
-    EBN_LAUNCH(topk_fill_empty_kernel, dim3(static_cast<unsigned>(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, out_pos, out_score, n);
-    EBN_CHECK_LAUNCH();
-    return EBN_OK;
-  }
+  if (M == 0) return topk_launch_fill_empty(out_pos, out_score, U, k, s);
   EBN_REQUIRE(users != nullptr && news_all != nullptr && n_rows >= 1, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(ebn_aligned16(users) && ebn_aligned16(news_all), EBN_ERR_ALIGN);
   if (exclude == nullptr) X = 0;
@@ -394,8 +259,6 @@ extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int
   a.out_pos = out_pos;
   a.out_score = out_score;
   a.flags = flags;
-  a.part_pos = nullptr;
-  a.part_score = nullptr;
   a.U = U;
   a.M = M;
   a.n_rows = n_rows;
@@ -405,14 +268,8 @@ extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int
   a.mode = mode;
   a.n_splits = splits;
   a.tiles_per_split = static_cast<int32_t>(ebn_ceil_div(ebn_ceil_div(M, TK_BN), splits));
-  if (splits > 1) {
-    const int64_t need = ebn_topk_workspace_bytes(U, k, splits);
-    EBN_REQUIRE(workspace != nullptr && workspace_bytes >= need, EBN_ERR_BAD_ARG);
-    EBN_REQUIRE(ebn_aligned16(workspace), EBN_ERR_ALIGN);
-    const int64_t n = static_cast<int64_t>(splits) * U * k;
-    a.part_pos = static_cast<int32_t*>(workspace);
-    a.part_score = reinterpret_cast<float*>(a.part_pos + n);
-  }
+  const int rc = topk_bind_workspace(a, splits, workspace, workspace_bytes);
+  if (rc != EBN_OK) return rc;
   const int64_t lds = topk_lds_bytes(k);
   // above the 64 KB a kernel may use without asking (k > 44); set per call: the attribute belongs to the current device
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -423,9 +280,6 @@ extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int
   EBN_LAUNCH(topk_score_kernel, dim3(static_cast<unsigned>(user_tiles), static_cast<unsigned>(splits)), dim3(TK_THREADS),
              static_cast<size_t>(lds), s, a);
   EBN_CHECK_LAUNCH();
-  if (splits > 1) {
-    EBN_LAUNCH(topk_merge_kernel, dim3(static_cast<unsigned>(ebn_ceil_div(U, 4))), dim3(256), 0, s, a);
-    EBN_CHECK_LAUNCH();
-  }
+  if (splits > 1) return topk_launch_merge(a, s);
   return EBN_OK;
 }

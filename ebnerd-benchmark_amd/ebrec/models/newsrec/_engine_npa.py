@@ -412,33 +412,29 @@ class NPAEngine:
         self._check_oob()
         return SimpleNamespace(Vd_all=Vd_all, Ua_all=Ua_all, n_rows=n_rows)
 
-    def score_cached(self, cache, user, his_idx, cand_idx, cand_imp, sigmoid=True):
-        """act(news(cand_i | user[cand_imp[i]]) . user_vec[cand_imp[i]]) of one indexed batch: user (b,) user indexes, his_idx (b, H) /
-        cand_idx (n,) rows of the cache, cand_imp (n,) the impression of each candidate.  User-table gather -> the two query
-        Dense -> indexed pooling of the b*H history slots -> the user stage of _encode, unchanged -> indexed pooling of the
-        candidates fused with the score (the candidate vectors are not written)."""
+    def _indexed_users(self, user, his_idx):
+        """(user (b,) indexes, his_idx (b, H) rows) of an indexed batch, checked on the host"""
         user = self._uidx(user)
         his_idx = np.asarray(his_idx)
         if his_idx.ndim != 2 or his_idx.shape[1] != self.H or user.shape[0] != his_idx.shape[0]:
             raise ValueError(f"indexed batches need user (b,) and his_idx (b, {self.H}), got {tuple(user.shape)} {tuple(his_idx.shape)}")
         self._host_ranges(user)
-        cand_idx, cand_imp = np.asarray(cand_idx).reshape(-1), np.asarray(cand_imp).reshape(-1)
-        if cand_idx.shape != cand_imp.shape:
-            raise ValueError(f"one impression per candidate: {cand_idx.shape} vs {cand_imp.shape}")
-        if cand_imp.size and (cand_imp.min() < 0 or cand_imp.max() >= his_idx.shape[0]):
-            raise IndexError(f"candidate impression out of range [0, {his_idx.shape[0]})")
+        return user, his_idx
+
+    def _user_state(self, cache, user, his_idx):
+        """The launches of user_state_cached() on checked arguments; the flags are left for the caller to read."""
         S = _hip.stream_handle
         call, pt, P = _hip.call, _hip.ptr, self.params
         f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
-        B, n, T, F, A, Du, H = his_idx.shape[0], cand_idx.shape[0], self.T, self.F, self.A, self.Du, self.H
+        B, T, F, A, Du, H = his_idx.shape[0], self.T, self.F, self.A, self.Du, self.H
         dev = self.device
         f = lambda *s: torch.empty(*s, device=dev)
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        uidx, hi, ci, rows = i32(user), i32(his_idx.reshape(-1)), i32(cand_idx), i32(cand_imp)
+        uidx, hi = i32(user), i32(his_idx.reshape(-1))
         q_his = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(H)
         iota = torch.arange(B, dtype=torch.int32, device=dev)
         Eu, Qn, Qu, ones = f(B, Du), f(B, A), f(B, A), torch.ones(max(B, 1), device=dev)
-        NV_h, Uu, wu, user_vec, out = f(B * H, F), f(B * H, A), f(B * H), f(B, F), f(n)
+        NV_h, Uu, wu, user_vec = f(B * H, F), f(B * H, A), f(B * H), f(B, F)
         call("ebn_gather_rows_f32", pt(uidx), pt(self.user_table), pt(Eu), B, Du, self.n_users + 1, None, -1, f0,
              pt(self.user_oob_flag), S())
         for Q, Wq, bq in ((Qn, "n_Wq", "n_bq"), (Qu, "u_Wq", "u_bq")):  # Dense(A)(u_emb) = 1.bq + e.Wq, as _encode
@@ -449,9 +445,35 @@ class NPAEngine:
         call("ebn_gemm_f32", 0, 0, B * H, A, F, f1, pt(NV_h), F, pt(P.view("u_Wa")), A, f0, pt(Uu), A, S())
         call("ebn_pap_fwd_f32", pt(Uu), pt(P.view("u_ba")), pt(Qu), pt(iota), B, pt(NV_h), pt(user_vec), pt(wu), None, 0, B, H, F, A,
              None, -1, f0, S())
+        return user_vec, Qn
+
+    def user_state_cached(self, cache, user, his_idx):
+        """Everything of an indexed batch that depends on the impression alone -> (user_vec (b, F), Qn (b, A)): user (b,) user
+        indexes, his_idx (b, H) rows of the cache.  User-table gather -> the two query Dense -> indexed pooling of the b*H history
+        slots -> the user stage of _encode, unchanged.  Qn is the news-level query a candidate of the impression is pooled with."""
+        user, his_idx = self._indexed_users(user, his_idx)
+        out = self._user_state(cache, user, his_idx)
+        self._check_oob()
+        return out
+
+    def score_cached(self, cache, user, his_idx, cand_idx, cand_imp, sigmoid=True):
+        """act(news(cand_i | user[cand_imp[i]]) . user_vec[cand_imp[i]]) of one indexed batch: user (b,) user indexes, his_idx (b, H) /
+        cand_idx (n,) rows of the cache, cand_imp (n,) the impression of each candidate.  user_state_cached()'s launches -> indexed
+        pooling of the candidates fused with the score (the candidate vectors are not written)."""
+        user, his_idx = self._indexed_users(user, his_idx)
+        cand_idx, cand_imp = np.asarray(cand_idx).reshape(-1), np.asarray(cand_imp).reshape(-1)
+        if cand_idx.shape != cand_imp.shape:
+            raise ValueError(f"one impression per candidate: {cand_idx.shape} vs {cand_imp.shape}")
+        if cand_imp.size and (cand_imp.min() < 0 or cand_imp.max() >= his_idx.shape[0]):
+            raise IndexError(f"candidate impression out of range [0, {his_idx.shape[0]})")
+        call, pt = _hip.call, _hip.ptr
+        B, n = his_idx.shape[0], cand_idx.shape[0]
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        ci, rows, out = i32(cand_idx), i32(cand_imp), torch.empty(n, device=self.device)
+        user_vec, Qn = self._user_state(cache, user, his_idx)
         if n:
             call("ebn_pap_indexed_f32", pt(cache.Ua_all), pt(cache.Vd_all), cache.n_rows, pt(ci), pt(Qn), pt(rows), B, None, pt(user_vec),
-                 pt(out), 1 if sigmoid else 0, pt(self.row_oob_flag), n, T, F, A, S())
+                 pt(out), 1 if sigmoid else 0, pt(self.row_oob_flag), n, self.T, self.F, self.A, _hip.stream_handle())
         self._check_oob()
         return out
 

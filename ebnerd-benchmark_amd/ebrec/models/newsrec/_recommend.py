@@ -4,7 +4,7 @@
     ids = model.recommend(loader, candidate_ids, top_n=5)                    # [n_impressions, 5] article ids
     IntralistDiversity()(ids, lookup_dict=DeviceLookup(articles, ["emb"]), lookup_key="emb")
 
-All cacheable models score as act(user . news): the catalogue is encoded once, a batch costs its user vectors, and
+Most cacheable models score as act(user . news): the catalogue is encoded once, a batch costs its user vectors, and
 ``ebn_topk_score_f32`` scores a tile of users against the streamed candidates keeping only each user's best ``top_n`` -- the
 [users, candidates] score matrix is never materialised.  A model takes part by offering three hooks:
 
@@ -12,6 +12,15 @@ All cacheable models score as act(user . news): the catalogue is encoded once, a
     _recommend_index(loader)              -> {article id: row of news_all}  (host only: arguments are checked before the device works)
     _recommend_cache(loader)              -> (cache, news_all [n_rows, F] device tensor)
     _user_vectors_cached(cache, loader, i) -> (user [b, F] device tensor, his_rows [b, H] rows of news_all)
+
+and, where act(user . news) is not its score, a fourth that replaces the scoring launch (everything around it stays this module's):
+
+    _recommend_topk(cache, users, cand_rows, exclude, k, sigmoid, flags) -> (pos [U, k] int32, score [U, k] float32)
+
+with ``users`` the concatenated first results of ``_user_vectors_cached`` (whatever the model packs into a row) and the contract of
+``ebn_topk_score_f32`` for everything else.  ``_recommend_cache`` then returns, in place of ``news_all``, any device tensor with one
+leading row per catalogue row.  NPA is the one such model: its news vector depends on the user, a row is ``user_vec | Qn`` and the
+launch is ``ebn_npa_topk_score_f32`` (``npa_topk`` below, ``NPAModel.recommend_pairwise``).
 
 ``rerank=MMR(lookup, key, lam, pool)`` (ebrec/evaluation/rerank.py) diversifies the lists: the same launch keeps each user's best
 ``pool``, their positions are mapped to rows of the lookup's unit table on the device, and ``ebn_mmr_rerank_f32`` picks ``top_n`` of
@@ -142,6 +151,26 @@ def topk(users: torch.Tensor, news_all: torch.Tensor, cand_rows, exclude, k: int
     return pos, score
 
 
+def npa_topk(users: torch.Tensor, Q: torch.Tensor, Ua_all: torch.Tensor, Vd_all: torch.Tensor, cand_rows, exclude, k: int, sigmoid: bool,
+             flags: torch.Tensor, n_splits: int = 0):
+    """One ebn_npa_topk_score_f32 call on device tensors (users [U, F], Q [U, A], Ua_all [n_rows, L, A], Vd_all [n_rows, L, F])
+    -> (pos [U, k] int32, score [U, k] float32); ``flags`` accumulates."""
+    U, F = users.shape
+    n_rows, L, A = Ua_all.shape
+    M = n_rows if cand_rows is None else cand_rows.shape[0]
+    X = 0 if exclude is None else exclude.shape[1]
+    pos = torch.empty(U, k, dtype=torch.int32, device=users.device)
+    score = torch.empty(U, k, dtype=torch.float32, device=users.device)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_npa_topk_auto_splits(U, M, L))
+    ws_bytes = int(lib.ebn_topk_workspace_bytes(U, k, max(splits, 1)))  # the partial lists are ebn_topk_score_f32's
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=users.device)
+    _hip.call("ebn_npa_topk_score_f32", _hip.ptr(users), _hip.ptr(Q), _hip.ptr(Ua_all), _hip.ptr(Vd_all), n_rows, _hip.ptr(cand_rows), M,
+              _hip.ptr(exclude), X, k, 1 if sigmoid else 0, splits, _hip.ptr(pos), _hip.ptr(score), _hip.ptr(flags), _hip.ptr(ws),
+              ws.numel(), U, L, F, A, _hip.stream_handle())
+    return pos, score
+
+
 def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True, return_scores=False, scores="sigmoid", fill_id=-1,
               users_per_call=65536, rerank=None):
     """ids [n_impressions, top_n] of the loader's article ids: each impression's ``top_n`` best of ``candidate_ids`` (``None``:
@@ -183,6 +212,12 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     elif calibrated:
         shared = torch.from_numpy(given_target(rerank.target, rerank.lookup.label_vocabulary(rerank.key)).astype(np.float32)).to(device)
     need_his = exclude_history or from_history
+    sigmoid = scores == "sigmoid"
+    model_topk = getattr(model, "_recommend_topk", None)  # the scoring launch: the model's own, or act(user . news)
+    if model_topk is None:
+        launch = lambda u, ex, k: topk(u, news_all, cand_d, ex, k, sigmoid, flags)
+    else:
+        launch = lambda u, ex, k: model_topk(cache, u, cand_d, ex, k, sigmoid, flags)
     pos_out, score_out, users, his, pending = [], [], [], [], 0
 
     def flush():
@@ -193,9 +228,9 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
         hh = torch.cat(his).contiguous() if need_his else None
         ex = hh if exclude_history else None
         if rerank is None:
-            p, s = topk(u, news_all, cand_d, ex, top_n, scores == "sigmoid", flags)
+            p, s = launch(u, ex, top_n)
         else:  # the pool, its rows in the lookup's table (-1 stays -1), the greedy picks, and the picks' positions and scores
-            pp, ps = topk(u, news_all, cand_d, ex, pool, scores == "sigmoid", flags)
+            pp, ps = launch(u, ex, pool)
             pool_rows = torch.where(pp >= 0, row_of_pos[pp.clamp(min=0).long()], pp).contiguous()
             if not calibrated:
                 sel, _ = mmr_select(unit, pool_rows, ps, top_n, rerank.lam, flags)

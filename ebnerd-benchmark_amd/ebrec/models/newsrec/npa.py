@@ -12,7 +12,10 @@ Inputs are ``(user_indexes (B,1), his_input_title (B,H,T), pred_input_title (B,C
   * ``scorer.predict`` over an eval-mode loader encodes the loader's article matrix ONCE per call: the conv output ``Vd`` and the
     attention keys ``Ua = tanh(Vd.Wa + ba)`` of a title do not depend on the user (only the logits ``q(user) . Ua_l`` do), so a
     batch is scored from row numbers by an indexed pooling kernel.  ``scorer.cache_articles = False`` is the per-batch path, and a
-    catalogue above ``NPAModel.catalogue_max_bytes`` takes it too.
+    catalogue above ``NPAModel.catalogue_max_bytes`` takes it too;
+  * ``recommend_pairwise(loader, candidate_ids, top_n=...)`` gives each impression's top-N of one shared candidate list from the
+    same once-encoded catalogue: NPA has no per-article vector, so ``ebn_npa_topk_score_f32`` computes every (user, candidate)
+    pair's logits and dots on the matrix cores, pools and selects in one launch (``_recommend.py``); ``recommend`` still raises.
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ import torch
 from ._engine import glorot_uniform_np
 from ._engine_npa import NPAEngine
 from ._keras_like import ScorerModel, TrainModel
+from ._recommend import npa_topk, recommend
 
 
 class NPAModel:
@@ -107,9 +111,44 @@ class NPAModel:
     def recommend(self, loader, candidate_ids=None, **kwargs):
         """Not implemented.  The encoded catalogue of ``scorer.predict`` does not give a per-article vector to rank against: with a
         shared candidate list the score of a (user, candidate) pair is sum_l w_l (u . Vd_l) with user-dependent w, about
-        T * (F + A) MACs (36 kFLOP at npa-c1) per pair -- a different kernel from the top-k over news vectors of ``_recommend.py``."""
+        T * (F + A) MACs (36 kFLOP at npa-c1) per pair -- a different kernel from the top-k over news vectors of ``_recommend.py``.
+        ``recommend_pairwise`` is that kernel behind this method's signature."""
         raise NotImplementedError("NPAModel.recommend: NPA's news vector depends on the user (personalised attention, npa.py), so "
                                   "there is no per-article catalogue to rank against")
+
+    # -- top-N lists from the once-encoded catalogue (_recommend.py): every (user, candidate) pair is pooled and scored ------------
+    _recommend_loader_method = "user_index_eval_batch"
+
+    def _recommend_index(self, loader):
+        return loader.lookup_article_index
+
+    def _recommend_cache(self, loader):
+        """(cache, Vd_all): the catalogue of ``scorer.predict``.  Ranking has no per-batch fallback, so a catalogue that does not
+        fit raises."""
+        cache = self._build_article_cache(loader)
+        if cache is None:
+            need = self._engine.catalogue_bytes(np.asarray(loader.lookup_article_matrix).shape[0])
+            raise ValueError(f"the encoded catalogue needs {need} bytes, above catalogue_max_bytes = {self.catalogue_max_bytes}: "
+                             "recommend_pairwise ranks from the whole catalogue (raise catalogue_max_bytes)")
+        return cache, cache.Vd_all
+
+    def _user_vectors_cached(self, cache, loader, i):
+        """(user_vec | Qn [b, F + A], his_idx): what a candidate is scored with, one row per impression of eval batch i"""
+        user, his_idx = loader.user_index_eval_batch(i)[:2]
+        user_vec, Qn = self._engine.user_state_cached(cache, user, his_idx)
+        return torch.cat([user_vec, Qn], 1), his_idx
+
+    def _recommend_topk(self, cache, users, cand_rows, exclude, k, sigmoid, flags):
+        """The scoring launch of ``_recommend.recommend`` for rows ``user_vec | Qn``: ebn_npa_topk_score_f32."""
+        F = self._engine.F
+        return npa_topk(users[:, :F].contiguous(), users[:, F:].contiguous(), cache.Ua_all, cache.Vd_all, cand_rows, exclude, k, sigmoid,
+                        flags)
+
+    def recommend_pairwise(self, loader, candidate_ids=None, **kwargs):
+        """Each impression's top_n of one shared candidate list (``_recommend.recommend``: the same arguments, defaults, results and
+        errors as the other models' ``recommend``), every (user, candidate) pair scored by personalised pooling from the
+        once-encoded catalogue."""
+        return recommend(self, loader, candidate_ids, **kwargs)
 
     def train_step(self, user, his, pred, y):
         """One optimizer step on raw arrays; returns the batch loss (device tensor)."""

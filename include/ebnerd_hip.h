@@ -1003,6 +1003,40 @@ int ebn_topk_score_f32(const float* users, const float* news_all, int64_t n_rows
                        float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, int32_t F,
                        ebn_stream_t stream);
 
+/* ---- top-N recommendation for NPA from the once-encoded catalogue (the same workflow for npa.py: its news vector depends on the
+ * user -- layers.py:312-339 PersonalizedAttentivePooling -- so there is no [n_rows, F] catalogue for ebn_topk_score_f32) ------------
+ * Per user u and candidate row = cand_rows[c], from what NPAEngine.encode_catalogue keeps (Ua_all [n_rows, L, A] tanh'd attention
+ * keys, Vd_all [n_rows, L, F] conv outputs) and the user stage gives (Q [U, A] news-level queries, users [U, F] user vectors):
+ *   s_l = Q[u, :] . Ua_all[row, l, :];  w = softmax_l(s) (max-subtracted, layers.py:334-335; no masking: every token counts)
+ *   score[u, c] = sum_l w_l (users[u, :] . Vd_all[row, l, :])     ( = pooled(u, row) . users[u], npa.py:188-199 scorer)
+ * Both dot products in exact fp32 (MFMA fma chains in a fixed k order); neither the [U, M, L] logits and dots nor the [U, M] scores
+ * are written out: each user keeps its best k in the order (score descending, candidate position ascending).  A pair's score bits
+ * depend only on that user's two rows and that catalogue row's data -- not on the candidate's position, U, M, n_splits or the run.
+ * NOT bit-equal to ebn_pap_indexed_f32's score, which pools first and dots second (both are within rounding of the same value).
+ * cand_rows [M] rows of the catalogue, or NULL = rows 0 .. n_rows - 1 (then M == n_rows); duplicate rows are distinct candidates
+ * (with bit-equal scores).  exclude [U, X] (or NULL): candidate c is skipped for user u when cand_rows[c] equals any of
+ * exclude[u, :]; entries outside [0, n_rows) match nothing (-1 is the padding).  A cand_rows entry outside [0, n_rows) is never
+ * turned into an address: it is skipped and sets flags[0]; a NaN score never enters a list and sets flags[1]; +-inf rank like
+ * numbers.  flags [2] is only ever SET (the caller zeroes it and may let it accumulate over calls).  out_pos [U, k]: position in
+ * cand_rows (the row number when cand_rows is NULL), -1 in the empty trailing slots of a user with fewer than k admissible
+ * candidates; out_score [U, k]: the raw score (mode 0) or its sigmoid (mode 1, applied to the kept values only; ranking is always
+ * on the raw value), -inf in empty slots.  All offsets are 64-bit.
+ * Limits: 1 <= k <= 64, 0 <= X <= 256, 1 <= L <= 64, A % 4 == 0, 4 <= A <= 1024, F % 4 == 0, 4 <= F <= 4096 (EBN_ERR_UNSUPPORTED),
+ * users / Q / Ua_all / Vd_all 16-byte aligned (EBN_ERR_ALIGN), NULL pointers or negative sizes EBN_ERR_BAD_ARG; all checked on the
+ * host before anything is launched, a failing call writes nothing.  U == 0: nothing to do; M == 0: the outputs are filled as empty.
+ * L is padded inside the kernel to the 32-row tile only (32, or 64 for L > 32): padded tokens get weight 0 and are never read.
+ * The grid is 128-user tiles x n_splits ranges of candidate steps (4 candidates a step for L <= 32, 2 above; n_splits 0 =
+ * ebn_npa_topk_auto_splits; clamped to the number of steps and to 64).  More than one range: each writes a partial list to the
+ * workspace -- the layout of ebn_topk_score_f32: 16-byte aligned, at least ebn_topk_workspace_bytes(U, k, n_splits) bytes, else
+ * EBN_ERR_BAD_ARG -- and a second launch merges them in the same total order.  No atomics; the result is bit-identical for every
+ * n_splits and from run to run.                                                                                                    */
+/* The number of candidate ranges n_splits = 0 stands for.  Pure host query, >= 1.                                                  */
+int ebn_npa_topk_auto_splits(int64_t n_users, int64_t n_cand, int32_t L);
+int ebn_npa_topk_score_f32(const float* users, const float* Q, const float* Ua_all, const float* Vd_all, int64_t n_rows,
+                           const int32_t* cand_rows, int64_t M, const int32_t* exclude, int32_t X, int32_t k, int32_t mode,
+                           int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace,
+                           int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A, ebn_stream_t stream);
+
 /* ---- MMR re-ranking of a relevance pool (greedy Maximal Marginal Relevance over the distance of IntralistDiversity,
  * beyond_accuracy.py:81-96: the list a top-N of ebn_topk_score_f32 with k = P becomes when relevance is traded against diversity) ---
  * Per user u of U: P pool entries, relevance pool_rel[u, i] and row pool_rows[u, i] of the UNIT table unit [n_rows, D] (what
