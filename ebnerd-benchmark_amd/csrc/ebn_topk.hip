@@ -21,6 +21,15 @@
 // the split, partial lists are merged in the same order by a second launch.  Bit-identical for every n_splits and from run to run.
 // Ranking is on the raw dot product; the sigmoid is applied to the k kept values when they are written.
 // The list code (LDS plan, drain and insert, write-out, merge and fill launches) is ebn_topk_list.h, shared with ebn_npa_topk.hip.
+//
+// Windowed form (ebn_topk_score_window_f32, the WINDOWED instantiation): user u may only receive the candidate positions of
+// window[u] = [lo, hi), clamped to [0, M).  The workgroup keeps its 128 users' clamped ranges in LDS behind the list plan (1 KB),
+// reduces them to their union [wlo, whi) and walks only the candidate tiles that meet it, dealt evenly over the n_splits ranges of
+// ITS OWN tile span -- with the candidates sorted by what the windows are about (publish time) and the users of a launch sorted
+// alike, the cost follows the window, not the catalogue.  A wave whose 32 users' union misses a visited tile only takes the
+// barriers; an accumulator element is a survivor only when its column also lies in its row's window (a tile inside every window of
+// the wave takes the plain compare), so nothing outside a window reaches the queue, the NaN flag or the lists.  A pair's dot
+// product is the same fma chain as in the plain form: the same bits, whatever the windows, the split and the other users are.
 #include "ebn_topk_list.h"
 
 namespace {
@@ -37,9 +46,13 @@ struct TopkArgs : TopkList {
   const int32_t* cand_rows;
   int64_t M, n_rows;
   int32_t F, tiles_per_split;
+  const int32_t* window;  // [U, 2] (lo, hi) candidate positions; the WINDOWED instantiation only
 };
 
-// dynamic LDS layout: ebn_topk_list.h
+constexpr int TK_WINDOW_LDS_BYTES = 2 * TK_BM * 4;  // lo[128] | hi[128] behind the plan of ebn_topk_list.h
+
+// dynamic LDS layout: ebn_topk_list.h (WINDOWED: + lo[128] | hi[128])
+template <bool WINDOWED>
 __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -75,10 +88,77 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
   bool saw_nan = false;
 
   const int64_t n_tiles = (a.M + TK_BN - 1) / TK_BN;
-  const int64_t t_beg = static_cast<int64_t>(split) * a.tiles_per_split;
+  int64_t t_beg = static_cast<int64_t>(split) * a.tiles_per_split;
   int64_t t_end = t_beg + a.tiles_per_split;
   t_end = t_end < n_tiles ? t_end : n_tiles;
   const int nk = (F + TK_BK - 1) / TK_BK;
+
+  // WINDOWED: the users' clamped ranges (an empty one, and a row past the last user, is [0, 0): no column passes), the union of
+  // the workgroup [wlo, whi) and of this wave [vlo, vhi) over the non-empty ones, the intersection of this wave [ilo, ihi) over
+  // its users below U.  All of them are wave-uniform.
+  volatile int* win_lo = lds.lps + TK_BM * k;  // the end of the plan: topk_lds_bytes(k)
+  volatile int* win_hi = win_lo + TK_BM;
+  int wlo = 0, whi = 0, vlo = 0, vhi = 0, ilo = 0, ihi = 0;
+  if constexpr (WINDOWED) {
+    if (tid < TK_BM) {
+      const int64_t u = u0 + tid;
+      int lo = 0, hi = 0;
+      if (u < a.U) {
+        lo = a.window[2 * u];
+        hi = a.window[2 * u + 1];
+        lo = lo > 0 ? lo : 0;
+        hi = static_cast<int64_t>(hi) < a.M ? hi : static_cast<int>(a.M);  // M <= INT32_MAX
+        if (lo >= hi) lo = hi = 0;
+      }
+      win_lo[tid] = lo;
+      win_hi[tid] = hi;
+    }
+    __syncthreads();
+    // lane l: rows l and l + 64 for the workgroup, row 32 wave + (l & 31) for the wave
+    int ulo = INT32_MAX, uhi = 0, xlo = INT32_MAX, xhi = 0, nlo = 0, nhi = INT32_MAX;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int lo = win_lo[lane + 64 * i], hi = win_hi[lane + 64 * i];
+      if (lo < hi) {
+        ulo = lo < ulo ? lo : ulo;
+        uhi = hi > uhi ? hi : uhi;
+      }
+    }
+    {
+      const int row = wave * 32 + il;
+      const int lo = win_lo[row], hi = win_hi[row];
+      if (lo < hi) {
+        xlo = lo;
+        xhi = hi;
+      }
+      if (u0 + row < a.U) {
+        nlo = lo;
+        nhi = hi;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const int o0 = __shfl_xor(ulo, off, 64), o1 = __shfl_xor(uhi, off, 64), o2 = __shfl_xor(xlo, off, 64);
+      const int o3 = __shfl_xor(xhi, off, 64), o4 = __shfl_xor(nlo, off, 64), o5 = __shfl_xor(nhi, off, 64);
+      ulo = o0 < ulo ? o0 : ulo;
+      uhi = o1 > uhi ? o1 : uhi;
+      xlo = o2 < xlo ? o2 : xlo;
+      xhi = o3 > xhi ? o3 : xhi;
+      nlo = o4 > nlo ? o4 : nlo;
+      nhi = o5 < nhi ? o5 : nhi;
+    }
+    wlo = __builtin_amdgcn_readfirstlane(ulo);
+    whi = __builtin_amdgcn_readfirstlane(uhi);
+    vlo = __builtin_amdgcn_readfirstlane(xlo);
+    vhi = __builtin_amdgcn_readfirstlane(xhi);
+    ilo = __builtin_amdgcn_readfirstlane(nlo);
+    ihi = __builtin_amdgcn_readfirstlane(nhi);
+    // the tiles that meet the union (none: wlo = INT32_MAX, whi = 0), dealt evenly over the splits
+    const int64_t w_beg = wlo / TK_BN, w_end = wlo < whi ? (static_cast<int64_t>(whi) + TK_BN - 1) / TK_BN : w_beg;
+    const int64_t w_n = w_end - w_beg;
+    t_beg = w_beg + w_n * split / a.n_splits;
+    t_end = w_beg + w_n * (split + 1) / a.n_splits;
+  }
 
   for (int64_t t = t_beg; t < t_end; ++t) {
     const int64_t n0 = t * TK_BN;
@@ -90,7 +170,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
         const int64_t r = a.cand_rows != nullptr ? static_cast<int64_t>(a.cand_rows[c]) : c;
         if (r < 0 || r >= a.n_rows) {
           row = -1;  // never turned into an address
-          a.flags[0] = 1;
+          if (!WINDOWED || (c >= wlo && c < whi)) a.flags[0] = 1;  // a visited tile also has columns outside the union
         } else {
           row = static_cast<int>(r);
         }
@@ -155,30 +235,47 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
       }
     };
 
+    // WINDOWED: a wave none of whose users' windows meets the tile fills the operand images and takes the barriers, nothing else
+    const bool wave_on = !WINDOWED || (n0 < vhi && n0 + TK_BN > vlo);
     fetch(0);
     store(0);
     __syncthreads();
     for (int kt = 0; kt < nk; kt += 2) {
       if (kt + 1 < nk) fetch(kt + 1);
-      mma(0);
+      if (wave_on) mma(0);
       if (kt + 1 < nk) store(1);
       __syncthreads();
       if (kt + 1 < nk) {
         if (kt + 2 < nk) fetch(kt + 2);
-        mma(1);
+        if (wave_on) mma(1);
         if (kt + 2 < nk) store(0);
         __syncthreads();
       }
     }
+    if (!wave_on) continue;
 
     // ---- selection.  C/D map of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const int rbase = wave * 32 + 4 * kl;
+    // WINDOWED: the column must lie in the row's window as well -- unless the tile is inside every window of this wave's users
+    const bool gated = WINDOWED && !(n0 >= ilo && n0 + TK_BN <= ihi);
+    const int c0 = static_cast<int>(n0) + il;  // this lane's column of MFMA tile 0
     bool any = false;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float th = thr[rbase + (r & 3) + 8 * (r >> 2)];
+      const int rl = rbase + (r & 3) + 8 * (r >> 2);
+      const float th = thr[rl];
+      // lo <= c < hi as ONE unsigned compare: (c - lo) < (hi - lo); 0 <= lo <= hi <= M and c < 2^31, nothing wraps
+      int d = 0;
+      unsigned w = UINT32_MAX;
+      if constexpr (WINDOWED) {
+        if (gated) {
+          const int lo = win_lo[rl];
+          d = c0 - lo;
+          w = static_cast<unsigned>(win_hi[rl] - lo);
+        }
+      }
 #pragma unroll
-      for (int j = 0; j < TK_TN; ++j) any |= !(acc[j][r] < th);
+      for (int j = 0; j < TK_TN; ++j) any |= !(acc[j][r] < th) && (!WINDOWED || static_cast<unsigned>(d + 32 * j) < w);
     }
     if (__ballot(any) == 0ull) continue;
 
@@ -186,10 +283,19 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
     for (int r = 0; r < 16; ++r) {
       const int rl = rbase + (r & 3) + 8 * (r >> 2);
       const float th = thr[rl];
+      int d = 0;
+      unsigned w = UINT32_MAX;
+      if constexpr (WINDOWED) {
+        if (gated) {
+          const int lo = win_lo[rl];
+          d = c0 - lo;
+          w = static_cast<unsigned>(win_hi[rl] - lo);
+        }
+      }
       int cnt = 0;
 #pragma unroll
       for (int j = 0; j < TK_TN; ++j) {
-        const bool pass = !(acc[j][r] < th);
+        const bool pass = !(acc[j][r] < th) && (!WINDOWED || static_cast<unsigned>(d + 32 * j) < w);
         const unsigned long long m = __ballot(pass);
         if (pass) {
           const int slot = cnt + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
@@ -233,16 +339,20 @@ extern "C" int64_t ebn_topk_workspace_bytes(int64_t n_users, int32_t k, int32_t 
   return ebn_sat_add(ebn_sat_mul(ebn_sat_mul(ebn_sat_mul(s, n_users), k), 8), 16);
 }
 
-extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int64_t n_rows, const int32_t* cand_rows, int64_t M,
-                                  const int32_t* exclude, int32_t X, int32_t k, int32_t mode, int32_t n_splits, int32_t* out_pos,
-                                  float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, int32_t F,
-                                  ebn_stream_t stream) {
+namespace {
+
+// both entry points: the checks, the plan and the launches; WINDOWED adds the window argument and 1 KB of LDS
+template <bool WINDOWED>
+int topk_score(const float* users, const float* news_all, int64_t n_rows, const int32_t* cand_rows, int64_t M, const int32_t* window,
+               const int32_t* exclude, int32_t X, int32_t k, int32_t mode, int32_t n_splits, int32_t* out_pos, float* out_score,
+               int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, int32_t F, ebn_stream_t stream) {
   EBN_REQUIRE(ebn_dim_ok(U, M, n_rows) && F >= 0 && X >= 0 && n_splits >= 0 && workspace_bytes >= 0, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(mode == 0 || mode == 1, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(k >= 1 && k <= TK_MAX_K && X <= TK_MAX_X && F >= 4 && F % 4 == 0 && F <= TK_MAX_F, EBN_ERR_UNSUPPORTED);
   EBN_REQUIRE(cand_rows != nullptr || M == n_rows, EBN_ERR_BAD_ARG);
   if (U == 0) return EBN_OK;
   EBN_REQUIRE(out_pos != nullptr && out_score != nullptr && flags != nullptr, EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(!WINDOWED || window != nullptr, EBN_ERR_BAD_ARG);
   hipStream_t s = ebn_stream(stream);
   if (M == 0) return topk_launch_fill_empty(out_pos, out_score, U, k, s);
   EBN_REQUIRE(users != nullptr && news_all != nullptr && n_rows >= 1, EBN_ERR_BAD_ARG);
@@ -255,6 +365,7 @@ extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int
   a.users = users;
   a.news = news_all;
   a.cand_rows = cand_rows;
+  a.window = window;
   a.exclude = exclude;
   a.out_pos = out_pos;
   a.out_score = out_score;
@@ -270,16 +381,35 @@ extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int
   a.tiles_per_split = static_cast<int32_t>(ebn_ceil_div(ebn_ceil_div(M, TK_BN), splits));
   const int rc = topk_bind_workspace(a, splits, workspace, workspace_bytes);
   if (rc != EBN_OK) return rc;
-  const int64_t lds = topk_lds_bytes(k);
+  constexpr int extra = WINDOWED ? TK_WINDOW_LDS_BYTES : 0;
+  const int64_t lds = topk_lds_bytes(k) + extra;
   // above the 64 KB a kernel may use without asking (k > 44); set per call: the attribute belongs to the current device
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(topk_lds_bytes(TK_MAX_K))) != hipSuccess) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_score_kernel<WINDOWED>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(topk_lds_bytes(TK_MAX_K)) + extra) != hipSuccess) {
     (void)hipGetLastError();
     return EBN_ERR_UNSUPPORTED;
   }
-  EBN_LAUNCH(topk_score_kernel, dim3(static_cast<unsigned>(user_tiles), static_cast<unsigned>(splits)), dim3(TK_THREADS),
+  EBN_LAUNCH(topk_score_kernel<WINDOWED>, dim3(static_cast<unsigned>(user_tiles), static_cast<unsigned>(splits)), dim3(TK_THREADS),
              static_cast<size_t>(lds), s, a);
   EBN_CHECK_LAUNCH();
   if (splits > 1) return topk_launch_merge(a, s);
   return EBN_OK;
+}
+
+}  // namespace
+
+extern "C" int ebn_topk_score_f32(const float* users, const float* news_all, int64_t n_rows, const int32_t* cand_rows, int64_t M,
+                                  const int32_t* exclude, int32_t X, int32_t k, int32_t mode, int32_t n_splits, int32_t* out_pos,
+                                  float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, int32_t F,
+                                  ebn_stream_t stream) {
+  return topk_score<false>(users, news_all, n_rows, cand_rows, M, nullptr, exclude, X, k, mode, n_splits, out_pos, out_score, flags,
+                           workspace, workspace_bytes, U, F, stream);
+}
+
+extern "C" int ebn_topk_score_window_f32(const float* users, const float* news_all, int64_t n_rows, const int32_t* cand_rows, int64_t M,
+                                         const int32_t* window, const int32_t* exclude, int32_t X, int32_t k, int32_t mode,
+                                         int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace,
+                                         int64_t workspace_bytes, int64_t U, int32_t F, ebn_stream_t stream) {
+  return topk_score<true>(users, news_all, n_rows, cand_rows, M, window, exclude, X, k, mode, n_splits, out_pos, out_score, flags,
+                          workspace, workspace_bytes, U, F, stream);
 }

@@ -29,6 +29,11 @@ them greedily by lam * score + (1 - lam) * (distance to the nearest item already
 way, ``ebn_label_target_f32`` turns the batch's history rows (mapped to the lookup's rows through one host-built int32 map) into
 each user's target label distribution, and ``ebn_calibrated_rerank_f32`` picks ``top_n`` greedily by
 lam * score - (1 - lam) * KL(target || the list's label distribution).
+
+``window=Freshness(published, max_age, min_age)`` (ebrec/evaluation/freshness.py) restricts every impression to the candidates
+published inside its own time window: the candidates are sorted by publish time, which makes an impression's admissible set one
+range [lo, hi) of positions, the users of a launch are sorted by ``lo``, and ``ebn_topk_score_window_f32`` lets a 128-user
+workgroup walk only the candidate tiles its users' ranges meet (``topk_window`` below).
 """
 from __future__ import annotations
 
@@ -36,6 +41,7 @@ import numpy as np
 import torch
 
 from ebrec import _hip
+from ebrec.evaluation.freshness import Freshness
 from ebrec.evaluation.rerank import (
     MAX_HISTORY, MAX_LABELS, MAX_POOL, MMR, Calibrated, calibrated_select, check_alpha, check_history_weights, check_lam,
     given_target, label_target, mmr_select,
@@ -151,6 +157,29 @@ def topk(users: torch.Tensor, news_all: torch.Tensor, cand_rows, exclude, k: int
     return pos, score
 
 
+def topk_window(users: torch.Tensor, news_all: torch.Tensor, cand_rows, window: torch.Tensor, exclude, k: int, sigmoid: bool,
+                flags: torch.Tensor, n_splits: int = 0):
+    """One ebn_topk_score_window_f32 call on device tensors: ``topk`` with window [U, 2] int32, user u may only receive the
+    candidate positions window[u, 0] <= c < window[u, 1] -> (pos [U, k] int32, score [U, k] float32); ``flags`` accumulates.
+    Cheapest with the users sorted by window[:, 0]: a workgroup of 128 users skips the candidate tiles none of their windows meets."""
+    U, F = users.shape
+    n_rows = news_all.shape[0]
+    M = n_rows if cand_rows is None else cand_rows.shape[0]
+    X = 0 if exclude is None else exclude.shape[1]
+    if window.shape != (U, 2) or window.dtype != torch.int32 or not window.is_contiguous():
+        raise ValueError(f"window must be a contiguous [{U}, 2] int32 tensor, got {tuple(window.shape)} {window.dtype}")
+    pos = torch.empty(U, k, dtype=torch.int32, device=users.device)
+    score = torch.empty(U, k, dtype=torch.float32, device=users.device)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_topk_auto_splits(U, M))
+    ws_bytes = int(lib.ebn_topk_workspace_bytes(U, k, max(splits, 1)))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=users.device)
+    _hip.call("ebn_topk_score_window_f32", _hip.ptr(users), _hip.ptr(news_all), n_rows, _hip.ptr(cand_rows), M, _hip.ptr(window),
+              _hip.ptr(exclude), X, k, 1 if sigmoid else 0, splits, _hip.ptr(pos), _hip.ptr(score), _hip.ptr(flags), _hip.ptr(ws),
+              ws.numel(), U, F, _hip.stream_handle())
+    return pos, score
+
+
 def npa_topk(users: torch.Tensor, Q: torch.Tensor, Ua_all: torch.Tensor, Vd_all: torch.Tensor, cand_rows, exclude, k: int, sigmoid: bool,
              flags: torch.Tensor, n_splits: int = 0):
     """One ebn_npa_topk_score_f32 call on device tensors (users [U, F], Q [U, A], Ua_all [n_rows, L, A], Vd_all [n_rows, L, F])
@@ -172,7 +201,7 @@ def npa_topk(users: torch.Tensor, Q: torch.Tensor, Ua_all: torch.Tensor, Vd_all:
 
 
 def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True, return_scores=False, scores="sigmoid", fill_id=-1,
-              users_per_call=65536, rerank=None):
+              users_per_call=65536, rerank=None, window=None):
     """ids [n_impressions, top_n] of the loader's article ids: each impression's ``top_n`` best of ``candidate_ids`` (``None``:
     every article of the loader's index) by the model's score, best first, ties by position in ``candidate_ids``.
     ``exclude_history`` drops the articles of the impression's own history; a list left shorter than ``top_n`` is padded with
@@ -187,13 +216,28 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     greedy calibrated order of the same pool (ebrec/evaluation/rerank.py): lam * score - (1 - lam) * KL(target || list) over the
     labels ``lookup`` holds under the label key ``key``.  The target is the label distribution of the impression's own history --
     needed even with ``exclude_history=False``; ``history_weights`` [H] weighs the loader's history slots -- or one given
-    {label: weight} dict / [C] array for everybody.  Scores as for MMR."""
+    {label: weight} dict / [C] array for everybody.  Scores as for MMR.
+    ``window=Freshness(published, max_age=None, min_age=0, time_col="impression_time")``: an impression at time t (its row of
+    ``loader.X[time_col]``) is only offered the candidates published in [t - max_age, t - min_age]; every candidate needs a publish
+    time.  The tie rule then reads: equal scores go to the OLDER article, then to the earlier position in ``candidate_ids``.  A
+    window holding fewer than ``top_n`` candidates gives a list padded with ``fill_id``; ``rerank=`` works on top unchanged (its
+    pool is the window's best, a history target is not touched by the window).  Not for models with a scoring launch of their
+    own (NPA)."""
+    if window is not None:
+        if getattr(model, "_recommend_topk", None) is not None:
+            raise NotImplementedError(f"window= is not supported for {type(model).__name__}: its scoring launch has no windowed form")
+        if not isinstance(window, Freshness):
+            raise ValueError(f"window must be None or a Freshness(published, max_age, min_age), got {type(window).__name__}")
     _check(model, loader, top_n, scores)
     top_n = int(top_n)
     index = model._recommend_index(loader)
     cand_ids, rows = candidate_rows(index, candidate_ids)
     if top_n > len(rows):
         raise ValueError(f"top_n = {top_n} is larger than the number of candidates ({len(rows)})")
+    if window is not None:  # the candidates by publish time from here on: positions, lookup rows and the final id mapping alike
+        order, win_lo, win_hi = window.windows(cand_ids, window.impression_times(loader))
+        cand_ids, rows = cand_ids[order], rows[order]
+        win_all = np.ascontiguousarray(np.stack([win_lo, win_hi], 1), dtype=np.int32)  # [n_impressions, 2], loader order
     if rerank is not None:
         pool, lookup_rows = _check_rerank(rerank, top_n, cand_ids)
     cache, news_all = model._recommend_cache(loader)
@@ -214,11 +258,13 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     need_his = exclude_history or from_history
     sigmoid = scores == "sigmoid"
     model_topk = getattr(model, "_recommend_topk", None)  # the scoring launch: the model's own, or act(user . news)
-    if model_topk is None:
-        launch = lambda u, ex, k: topk(u, news_all, cand_d, ex, k, sigmoid, flags)
+    if window is not None:
+        launch = lambda u, ex, k, w: topk_window(u, news_all, cand_d, w, ex, k, sigmoid, flags)
+    elif model_topk is None:
+        launch = lambda u, ex, k, w: topk(u, news_all, cand_d, ex, k, sigmoid, flags)
     else:
-        launch = lambda u, ex, k: model_topk(cache, u, cand_d, ex, k, sigmoid, flags)
-    pos_out, score_out, users, his, pending = [], [], [], [], 0
+        launch = lambda u, ex, k, w: model_topk(cache, u, cand_d, ex, k, sigmoid, flags)
+    pos_out, score_out, users, his, wins, pending = [], [], [], [], [], 0
 
     def flush():
         nonlocal pending
@@ -226,11 +272,17 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
             return
         u = torch.cat(users).contiguous()
         hh = torch.cat(his).contiguous() if need_his else None
+        wd = perm = None
+        if window is not None:  # users, histories and windows sorted by lo (stable): neighbours share their candidate tiles
+            wd = torch.from_numpy(np.concatenate(wins)).to(device)
+            perm = torch.argsort(wd[:, 0], stable=True)
+            u, wd = u[perm].contiguous(), wd[perm].contiguous()
+            hh = hh[perm].contiguous() if need_his else None
         ex = hh if exclude_history else None
         if rerank is None:
-            p, s = launch(u, ex, top_n)
+            p, s = launch(u, ex, top_n, wd)
         else:  # the pool, its rows in the lookup's table (-1 stays -1), the greedy picks, and the picks' positions and scores
-            pp, ps = launch(u, ex, pool)
+            pp, ps = launch(u, ex, pool, wd)
             pool_rows = torch.where(pp >= 0, row_of_pos[pp.clamp(min=0).long()], pp).contiguous()
             if not calibrated:
                 sel, _ = mmr_select(unit, pool_rows, ps, top_n, rerank.lam, flags)
@@ -247,10 +299,13 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
             kept = sel.clamp(min=0).long()
             p = torch.where(sel >= 0, pp.gather(1, kept), sel)
             s = torch.where(sel >= 0, ps.gather(1, kept), torch.full_like(ps[:, :1], float("-inf")))
+        if perm is not None:  # back to loader order
+            p, s = torch.empty_like(p).index_copy_(0, perm, p), torch.empty_like(s).index_copy_(0, perm, s)
         pos_out.append(p)
         score_out.append(s)
         users.clear()
         his.clear()
+        wins.clear()
         pending = 0
 
     for i in range(len(loader)):
@@ -266,6 +321,11 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
             if his and his[0].shape[1] != h.shape[1]:
                 flush()
             his.append(h)
+        if window is not None:
+            w = win_all[i * loader.batch_size: i * loader.batch_size + user.shape[0]]
+            if len(w) != user.shape[0]:
+                raise ValueError(f"batch {i} has {user.shape[0]} impressions, the loader's frame holds {len(w)} rows for it")
+            wins.append(w)
         users.append(user)
         pending += user.shape[0]
         if pending >= users_per_call:

@@ -16,6 +16,7 @@ DEFAULT_TITLE_COL = "title"
 DEFAULT_SUBTITLE_COL = "subtitle"
 DEFAULT_BODY_COL = "body"
 DEFAULT_CATEGORY_COL = "category"
+DEFAULT_ARTICLE_PUBLISHED_TIMESTAMP_COL = "published_time"
 
 # history.parquet
 DEFAULT_HISTORY_ARTICLE_ID_COL = f"{DEFAULT_ARTICLE_ID_COL}_fixed"
