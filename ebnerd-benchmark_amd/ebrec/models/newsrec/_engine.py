@@ -17,39 +17,17 @@ Data layout in HBM (all fp32 row-major):
 from __future__ import annotations
 
 import ctypes
-import math
 
 import numpy as np
 import torch
 
 from ebrec import _hip
 
-BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-7  # tf.keras.optimizers.Adam defaults (nrms.py:77)
-_ALIGN = 64  # floats; keeps every parameter 256-byte aligned inside the flat buffer
-
+# the pieces every engine shares live in _engine_base.py (which imports nothing from here); they keep resolving from this module
+from ._engine_base import (ADAM_EPS, BCE_ON, BETA1, BETA2, LOSS_KIND, FlatParams, StepStateOwner, conv_glorot_np,  # noqa: F401
+                           glorot_uniform_np, loss_kind_of, pair_score_tail, require_gpu, score_loss_tail)
 from ._engine_segments import SegmentsMixin  # noqa: E402  (the multi-rank step: segments, collectives, the one-graph self-check)
 from ._engine_staging import StagingMixin  # noqa: E402  (device-side batch assembly: article rows -> token ids, pinned staging)
-
-LOSS_KIND = {"cross_entropy_loss": 0, "log_loss": 1}
-BCE_ON = ("logits", "probs")
-
-
-def loss_kind_of(loss: str, bce_on: str) -> int:
-    """C-ABI loss_kind: 0 categorical CE on the softmax logits; 1 log_loss as sigmoid-CE on the logits Keras caches on the
-    output of Activation("softmax") (bce_on="logits", the default); 2 log_loss as BCE on the clipped softmax outputs
-    (bce_on="probs", SURVEY.md A.5's reading).  Which of the two TF 2.12-2.15 runs at nrms.py:54,61-62 is settled by the TF
-    dump (tools/dump_tf_golden.py); until then both are implemented and tested, and switching is this one argument."""
-    if bce_on not in BCE_ON:
-        raise ValueError(f"bce_on must be one of {BCE_ON}, got {bce_on}")
-    return 0 if loss == "cross_entropy_loss" else (1 if bce_on == "logits" else 2)
-
-
-def require_gpu() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("the MI355X NRMS path needs a visible GPU (no CPU fallback); "
-                           "torch.cuda.is_available() is False")
-    _hip.lib()
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def eval_loss_from_news(eng, news_all: torch.Tensor, his_idx, pred_idx, y):
@@ -66,49 +44,7 @@ def eval_loss_from_news(eng, news_all: torch.Tensor, his_idx, pred_idx, y):
               ctypes.c_float(0.0), None, S())
     user = eng.encode_users_from_news(NE[: B * H].view(B, H, E))
     cand = NE[B * H:]
-    scores, probs = torch.empty(B, C, device=eng.device), torch.empty(B, C, device=eng.device)
-    _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user), _hip.ptr(scores), _hip.ptr(probs), B, C, E, 0, S())
-    labels = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(y, dtype=np.float32))))
-    labels = labels.to(device=eng.device, dtype=torch.float32).reshape(B, C).contiguous()
-    rows, junk_c, junk_u = torch.empty(B, device=eng.device), torch.empty(B * C, E, device=eng.device), torch.empty(B, E, device=eng.device)
-    loss = torch.empty(1, device=eng.device)
-    _hip.call("ebn_score_loss_bwd_f32", _hip.ptr(cand), _hip.ptr(user), _hip.ptr(scores), _hip.ptr(labels), _hip.ptr(rows),
-              _hip.ptr(junk_c), _hip.ptr(junk_u), B, C, E, eng.loss_kind, ctypes.c_float(1.0 / B), S())
-    _hip.call("ebn_sum_f32", _hip.ptr(rows), B, ctypes.c_float(1.0), _hip.ptr(loss), 0, S())
-    return loss, probs
-
-
-def glorot_uniform_np(shape, seed):
-    """[KERAS-SEMANTICS] GlorotUniform(seed): the same (seed, shape) gives the same draw, which is
-    why WQ, WK and WV of one layer start identical in the reference (layers.py:155-172)."""
-    rng = np.random.default_rng(seed)
-    lim = math.sqrt(6.0 / (shape[0] + shape[-1]))
-    return rng.uniform(-lim, lim, size=shape).astype(np.float32)
-
-
-class FlatParams:
-    """Named fp32 parameters carved out of one flat device buffer (plus grad / Adam moments)."""
-
-    def __init__(self, shapes: dict, device):
-        self.shapes = dict(shapes)
-        self.offsets = {}
-        off = 0
-        for name, shp in shapes.items():
-            self.offsets[name] = off
-            off += -(-int(np.prod(shp)) // _ALIGN) * _ALIGN
-        self.numel = off
-        self.data = torch.zeros(off, device=device)
-        self.grad = torch.zeros(off, device=device)
-        self.m = torch.zeros(off, device=device)
-        self.v = torch.zeros(off, device=device)
-
-    def view(self, name, buf=None):
-        buf = self.data if buf is None else buf
-        n = int(np.prod(self.shapes[name]))
-        return buf[self.offsets[name]: self.offsets[name] + n].view(*self.shapes[name])
-
-    def g(self, name):
-        return self.view(name, self.grad)
+    return score_loss_tail(cand, user, y, B, C, E, eng.loss_kind)[:2]
 
 
 class EncoderBuffers:
@@ -131,7 +67,7 @@ class EncoderBuffers:
         self.dX = f(R, Din) if need_dx else None
 
 
-class NRMSEngine(StagingMixin, SegmentsMixin):
+class NRMSEngine(StagingMixin, SegmentsMixin, StepStateOwner):
     def __init__(self, table: np.ndarray, title_size: int, history_size: int, head_num: int, head_dim: int,
                  attention_hidden_dim: int, dropout: float, learning_rate: float, loss: str, seed=None,
                  train_embedding: bool = True, device=None, process_group=None, shard_table: bool = False,
@@ -196,10 +132,7 @@ class NRMSEngine(StagingMixin, SegmentsMixin):
             self.table_v = torch.zeros_like(self.table)
             if self.deterministic:  # order-independent fixed-point accumulator of the embedding gradient
                 self.table_acc = torch.zeros(self.table.shape, dtype=torch.int64, device=self.device)
-        st = _hip.StepState()
-        st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
-        self.state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(self.device)
-        self._lr = float(learning_rate)
+        self._init_step_state(seed, learning_rate)
         self._bufs = {}
         self.oob_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.keep_table_grad = False  # True: always materialise the fp32 dense table gradient (inspection / tests)
@@ -245,10 +178,6 @@ class NRMSEngine(StagingMixin, SegmentsMixin):
     def multi(self) -> bool:
         """the step runs its multi-rank launch form (world > 1, or forced on a one-rank group: see `force_collectives`)"""
         return self.world > 1 or self.force_collectives
-
-    @property
-    def loss_kind(self) -> int:
-        return loss_kind_of(self.loss, self.bce_on)
 
     # ------------------------------------------------------------------ parameters
     def _init_weights(self, seed):
@@ -386,21 +315,6 @@ class NRMSEngine(StagingMixin, SegmentsMixin):
         if not flag:
             self._graphs = {}
         return self
-
-    # ------------------------------------------------------------------ optimizer state
-    @property
-    def learning_rate(self):
-        return self._lr
-
-    @learning_rate.setter
-    def learning_rate(self, lr):
-        self._lr = float(lr)
-        st = self.read_state()
-        st.lr = self._lr
-        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
-
-    def read_state(self):
-        return _hip.StepState.from_buffer_copy(self.state.cpu().numpy().tobytes())
 
     # ------------------------------------------------------------------ buffers
     def _news_bufs(self, N, train):
@@ -741,8 +655,8 @@ class NRMSEngine(StagingMixin, SegmentsMixin):
         NEh = self.encode_news(his.reshape(B * H, self.T))
         return self.encode_users_from_news(NEh.view(B, H, self.E))
 
-    def forward(self, his, pred, mode="softmax"):
-        """(B,H,T),(B,C,T) ids -> (probs (B,C), scores (B,C)) device tensors, inference mode."""
+    def _encode_batch(self, his, pred):
+        """Inference-mode encoders of one batch of (B,H,T), (B,C,T) ids: (candidate news vectors (B*C,E), user vectors (B,E), B, C)."""
         his = his if isinstance(his, torch.Tensor) else np.asarray(his)
         pred = pred if isinstance(pred, torch.Tensor) else np.asarray(pred)
         B, C = his.shape[0], pred.shape[1]
@@ -753,37 +667,27 @@ class NRMSEngine(StagingMixin, SegmentsMixin):
         self._news_forward(nb, N, False, B * self.H)
         ub = self._user_bufs(B, False)
         self._encoder_fwd("u", ub, B, nb.out, False)
+        return nb.out[B * self.H:], ub.out, B, C
+
+    def forward(self, his, pred, mode="softmax"):
+        """(B,H,T),(B,C,T) ids -> (probs (B,C), scores (B,C)) device tensors, inference mode."""
+        cand, user, B, C = self._encode_batch(his, pred)
         scores = torch.empty(B, C, device=self.device)
         probs = torch.empty(B, C, device=self.device)
-        cand = nb.out[B * self.H:]
-        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(ub.out), _hip.ptr(scores), _hip.ptr(probs), B, C,
+        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user), _hip.ptr(scores), _hip.ptr(probs), B, C,
                   self.E, 0 if mode == "softmax" else 1, _hip.stream_handle())
         self._check_oob()
         return probs, scores
 
     def eval_loss(self, his, pred, y):
         """Inference-mode forward + the compiled loss (validation pass of fit): (loss[1], probs (B,C))."""
-        probs, scores = self.forward(his, pred, mode="softmax")
-        B, C = scores.shape
-        labels = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(y, dtype=np.float32))))
-        labels = labels.to(device=self.device, dtype=torch.float32).reshape(B, C).contiguous()
-        nb, ub = self._news_bufs(B * (self.H + C), False), self._user_bufs(B, False)
-        rows = torch.empty(B, device=self.device)
-        junk_c = torch.empty(B * C, self.E, device=self.device)
-        junk_u = torch.empty(B, self.E, device=self.device)
-        loss = torch.empty(1, device=self.device)
-        _hip.call("ebn_score_loss_bwd_f32", _hip.ptr(nb.out[B * self.H:]), _hip.ptr(ub.out), _hip.ptr(scores),
-                  _hip.ptr(labels), _hip.ptr(rows), _hip.ptr(junk_c), _hip.ptr(junk_u), B, C, self.E,
-                  self.loss_kind, ctypes.c_float(1.0 / B), _hip.stream_handle())
-        _hip.call("ebn_sum_f32", _hip.ptr(rows), B, ctypes.c_float(1.0), _hip.ptr(loss), 0, _hip.stream_handle())
+        cand, user, B, C = self._encode_batch(his, pred)
+        loss, probs, _scores = score_loss_tail(cand, user, y, B, C, self.E, self.loss_kind)
+        self._check_oob()
         return loss, probs
 
     def pair_scores(self, user, news, u_idx, n_idx, sigmoid=True):
-        n = u_idx.numel()
-        out = torch.empty(n, device=self.device)
-        _hip.call("ebn_pair_score_f32", _hip.ptr(user), _hip.ptr(news), _hip.ptr(u_idx), _hip.ptr(n_idx),
-                  _hip.ptr(out), n, self.E, 1 if sigmoid else 0, _hip.stream_handle())
-        return out
+        return pair_score_tail(user, news, u_idx, n_idx, self.E, sigmoid)
 
     def _check_shapes(self, his, pred):
         if his.ndim != 3 or his.shape[1] != self.H or his.shape[2] != self.T:

@@ -18,10 +18,11 @@ import torch
 from ebrec import _hip
 
 from ._engine import ADAM_EPS, BETA1, BETA2, LOSS_KIND, loss_kind_of, EncoderBuffers, FlatParams, glorot_uniform_np, require_gpu
+from ._engine_base import StepStateOwner, pair_score_tail, score_loss_tail
 from ._mlp import MLPStack
 
 
-class DocVecEngine:
+class DocVecEngine(StepStateOwner):
     def __init__(self, doc_dim: int, units, history_size: int, head_num: int, head_dim: int, attention_hidden_dim: int,
                  dropout: float, learning_rate: float, loss: str, l2: float, seed=None, device=None, process_group=None,
                  bce_on: str = "logits"):
@@ -53,10 +54,7 @@ class DocVecEngine:
         self.mlp = MLPStack(self.params, "", self.Din, self.units, self.device, self.l2, on_realloc=lambda: self._graphs.clear())
         self.bn_mean, self.bn_var = self.mlp.bn_mean, self.mlp.bn_var
         self._init_weights(seed)
-        st = _hip.StepState()
-        st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
-        self.state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(self.device)
-        self._lr = float(learning_rate)
+        self._init_step_state(seed, learning_rate)
         self._bufs = {}
         self.loss_dev = torch.zeros(1, device=self.device)
         self.reg_dev = torch.zeros(1, device=self.device)
@@ -76,10 +74,6 @@ class DocVecEngine:
     @property
     def multi(self) -> bool:
         return self.world > 1 or self.force_collectives
-
-    @property
-    def loss_kind(self) -> int:
-        return loss_kind_of(self.loss, self.bce_on)
 
     # ------------------------------------------------------------------ parameters
     def _init_weights(self, seed):
@@ -120,20 +114,6 @@ class DocVecEngine:
 
     def count_params(self):
         return sum(int(np.prod(s)) for s in self.params.shapes.values()) + 2 * sum(self.units)
-
-    @property
-    def learning_rate(self):
-        return self._lr
-
-    @learning_rate.setter
-    def learning_rate(self, lr):
-        self._lr = float(lr)
-        st = self.read_state()
-        st.lr = self._lr
-        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
-
-    def read_state(self):
-        return _hip.StepState.from_buffer_copy(self.state.cpu().numpy().tobytes())
 
     # ------------------------------------------------------------------ buffers
     def _mlp_bufs(self, N):
@@ -361,7 +341,8 @@ class DocVecEngine:
         B, H = his.shape[0], his.shape[1]
         return self.encode_users_from_news(self.encode_news(his.reshape(B * H, self.Din)).view(B, H, self.E))
 
-    def forward(self, his, pred, mode="softmax"):
+    def _encode_batch(self, his, pred):
+        """Inference-mode encoders of one batch: (candidate news vectors (B*C,E), user vectors (B,E), B, C)."""
         his = his if isinstance(his, torch.Tensor) else np.asarray(his)
         pred = pred if isinstance(pred, torch.Tensor) else np.asarray(pred)
         self._check_shapes(his, pred)
@@ -371,29 +352,21 @@ class DocVecEngine:
         self._news_forward(mb, n_hist, n_cand, False)
         dims, params, acts = self._enc(ub, B, mb["NE"])
         _hip.call("ebn_encoder_fwd_f32", ctypes.byref(dims), ctypes.byref(params), ctypes.byref(acts), ctypes.byref(self._fwd_scratch(ub)), None, _hip.stream_handle())
+        return mb["NE"][n_hist:], ub.out, B, C
+
+    def forward(self, his, pred, mode="softmax"):
+        cand, user, B, C = self._encode_batch(his, pred)
         scores, probs = torch.empty(B, C, device=self.device), torch.empty(B, C, device=self.device)
-        _hip.call("ebn_score_fwd_f32", _hip.ptr(mb["NE"][n_hist:]), _hip.ptr(ub.out), _hip.ptr(scores), _hip.ptr(probs), B, C,
+        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user), _hip.ptr(scores), _hip.ptr(probs), B, C,
                   self.E, 0 if mode == "softmax" else 1, _hip.stream_handle())
         return probs, scores
 
     def eval_loss(self, his, pred, y):
-        probs, scores = self.forward(his, pred)
-        B, C = scores.shape
-        labels = torch.as_tensor(np.asarray(y, dtype=np.float32)).to(self.device).reshape(B, C).contiguous()
-        mb, ub = self._mlp_bufs(B * (self.H + C)), self._user_bufs(B)
-        rows, jc, ju = torch.empty(B, device=self.device), torch.empty(B * C, self.E, device=self.device), torch.empty(B, self.E, device=self.device)
-        loss = torch.empty(1, device=self.device)
-        _hip.call("ebn_score_loss_bwd_f32", _hip.ptr(mb["NE"][B * self.H:]), _hip.ptr(ub.out), _hip.ptr(scores), _hip.ptr(labels),
-                  _hip.ptr(rows), _hip.ptr(jc), _hip.ptr(ju), B, C, self.E, self.loss_kind, ctypes.c_float(1.0 / B), _hip.stream_handle())
-        _hip.call("ebn_sum_f32", _hip.ptr(rows), B, ctypes.c_float(1.0), _hip.ptr(loss), 0, _hip.stream_handle())
-        return loss, probs
+        cand, user, B, C = self._encode_batch(his, pred)
+        return score_loss_tail(cand, user, y, B, C, self.E, self.loss_kind)[:2]
 
     def pair_scores(self, user, news, u_idx, n_idx, sigmoid=True):
-        n = u_idx.numel()
-        out = torch.empty(n, device=self.device)
-        _hip.call("ebn_pair_score_f32", _hip.ptr(user), _hip.ptr(news), _hip.ptr(u_idx), _hip.ptr(n_idx), _hip.ptr(out), n,
-                  self.E, 1 if sigmoid else 0, _hip.stream_handle())
-        return out
+        return pair_score_tail(user, news, u_idx, n_idx, self.E, sigmoid)
 
     def enable_graphs(self, flag=True):
         """Capture the per-(B, C) kernel sequence of a train step into a hipGraph (the DocVec step is ~70 small

@@ -16,6 +16,10 @@ Data layout in HBM (fp32 row-major):
                                    gru_r (U, 3U), gru_b (2, 3U) [, dense_W (2U, U), dense_b (U,) for "con"] -> one Adam launch
   titles       N = B*(H+C) per step, history titles first (b*H + h), then candidates (B*H + b*C + c)
   GRU          Hs (H+1, B, U) time-major states, act (H, B, 4U) gate activations, gx / dgx (B*H, 3U), dgh (H, B, 3U)
+
+Shared with the other engines and defined in _engine_base.py: constructor scaffolding, step state, flags (_check_oob), staging and
+train_step, forward / eval_loss / pair_scores, the Adam launches, the Conv1D backward block (UserTableEngine <- ConvEngineBase).  Here:
+buffers, shapes, weight order, the encoders, the backward up to the Conv1D, and scoring from an encoded catalogue.
 """
 from __future__ import annotations
 
@@ -27,8 +31,7 @@ import torch
 
 from ebrec import _hip
 
-from ._engine import ADAM_EPS, BETA1, BETA2, FlatParams, glorot_uniform_np, loss_kind_of, require_gpu
-from ._engine_npa import conv_glorot_np
+from ._engine_base import BETA1, BETA2, ConvView, UserTableEngine, glorot_uniform_np, pair_score_tail
 
 SITE_NEWS_IN, SITE_CONV = 0, 2
 
@@ -68,65 +71,37 @@ class _Bufs:
             self.ws = f(max(int(wsf(F, A, R)), int(wsf(U, 3 * U, BH)), int(wsf(F, 3 * U, BH)), int(wsf(1, 3 * U, BH)), 1))
 
 
-class LSTUREngine:
+class LSTUREngine(UserTableEngine):
+    MODEL = "LSTUR"
+
     def __init__(self, table: np.ndarray, n_users: int, title_size: int, history_size: int, filter_num: int, window_size: int,
                  attention_hidden_dim: int, gru_unit: int, user_type: str, dropout: float, learning_rate: float, loss: str,
                  seed=None, train_embedding: bool = True, device=None, process_group=None, bce_on: str = "logits"):
-        if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
-            raise ValueError("LSTURModel runs on one rank: multi-rank LSTUR is not implemented (build it without a process group "
-                             "of more than one rank)")
+        self._require_one_rank(process_group)
         if user_type not in TYPES:
             raise ValueError(f"LSTUR type must be 'ini' or 'con', got {user_type!r}")
         if int(filter_num) != int(gru_unit):
             raise ValueError(f"filter_num ({filter_num}) must equal gru_unit ({gru_unit}): the score is cand . user")
-        self.device = require_gpu() if device is None else torch.device(device)
-        table = np.asarray(table, dtype=np.float32)
-        self.V, self.E = table.shape
+        self._init_table(table, device)
         self.n_users, self.type = int(n_users), user_type
         self.T, self.H, self.F, self.A, self.window = int(title_size), int(history_size), int(filter_num), int(attention_hidden_dim), int(window_size)
         self.U = int(gru_unit)
         if self.E % 4 or self.F % 4:
             raise ValueError(f"word_emb_dim ({self.E}) and filter_num ({self.F}) must be multiples of 4 for the HIP Conv1D and GRU")
-        self.p = float(dropout)
-        self.loss, self.bce_on = loss, bce_on
-        loss_kind_of(loss, bce_on)
-        self.train_embedding = bool(train_embedding)
-        self.seed = seed
-        dev = self.device
         W, E, F, A, U = self.window, self.E, self.F, self.A, self.U
         shapes = {"conv_Wb": (W * E + 1, F), "att_W": (F, A), "att_b": (A,), "att_q": (A,), "gru_k": (F, 3 * U),
                   "gru_r": (U, 3 * U), "gru_b": (2, 3 * U)}
         if self.type == "con":
             shapes.update({"dense_W": (2 * U, U), "dense_b": (U,)})
-        self.params = FlatParams(shapes, dev)
-        self.table = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
-        self.user_table = torch.zeros(self.n_users + 1, U, device=dev)  # embeddings_initializer="zeros" (lstur.py:71-76)
-        self.table_acc = torch.zeros(self.table.numel(), dtype=torch.int64, device=dev)
-        self.table_m, self.table_v = torch.zeros_like(self.table), torch.zeros_like(self.table)
-        self.user_acc = torch.zeros(self.user_table.numel(), dtype=torch.int64, device=dev)
-        self.user_m, self.user_v = torch.zeros_like(self.user_table), torch.zeros_like(self.user_table)
-        self.oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.user_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.row_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)  # a history row outside an encoded catalogue
-        self.loss_dev = torch.zeros(1, device=dev)
-        st = _hip.StepState()
-        st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
-        self.state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev)
-        self._lr = float(learning_rate)
-        self._bufs, self._graphs = {}, {}
-        self.use_graph = True
-        self.article_matrix = None
-        self._article_matrix_src = None
+        self._init_state(shapes, U, dropout, learning_rate, loss, seed, train_embedding, bce_on)  # user table: lstur.py:71-76
         self._init_weights(seed)
 
     # ------------------------------------------------------------------ parameters
     def _init_weights(self, seed):
         pv = self.params.view
-        W, E, F, A, U = self.window, self.E, self.F, self.A, self.U
+        F, A, U = self.F, self.A, self.U
+        self._conv_init("conv_Wb", seed)
         with torch.no_grad():
-            pv("conv_Wb")[: W * E].copy_(torch.from_numpy(conv_glorot_np(W, E, F, seed).reshape(W * E, F)))
-            pv("conv_Wb")[W * E].zero_()
             pv("att_W").copy_(torch.from_numpy(glorot_uniform_np((F, A), seed)))
             pv("att_q").copy_(torch.from_numpy(glorot_uniform_np((A, 1), seed).reshape(A)))
             # kernel (F, 3U) and recurrent kernel (U, 3U) are glorot_uniform(seed) of one shape: identical at init (F == U)
@@ -146,9 +121,8 @@ class LSTUREngine:
 
     def get_weights(self):
         pv = lambda n: self.params.view(n).cpu().numpy()
-        W, E, F, A = self.window, self.E, self.F, self.A
-        wb = pv("conv_Wb")
-        out = [self.table.cpu().numpy(), self.user_table.cpu().numpy(), wb[: W * E].reshape(W, E, F).copy(), wb[W * E].copy()]
+        A = self.A
+        out = [self.table.cpu().numpy(), self.user_table.cpu().numpy()] + self._conv_get("conv_Wb")
         for name in self._dense_names():
             a = pv(name)
             out.append(a.reshape(A, 1) if name == "att_q" else a)
@@ -170,8 +144,7 @@ class LSTUREngine:
             self.table.copy_(t(w[0]))
             self.user_table.copy_(t(w[1]))
             pv = self.params.view
-            pv("conv_Wb")[: W * E].copy_(t(w[2].reshape(W * E, F)))
-            pv("conv_Wb")[W * E].copy_(t(w[3]))
+            self._conv_set("conv_Wb", w[2], w[3])
             for name, a in zip(self._dense_names(), w[4:]):
                 pv(name).copy_(t(a.reshape(pv(name).shape)))
 
@@ -179,34 +152,6 @@ class LSTUREngine:
         W, E, F, A, U = self.window, self.E, self.F, self.A, self.U
         n = self.table.numel() + self.user_table.numel() + W * E * F + F + F * A + 2 * A + 3 * U * F + 3 * U * U + 6 * U
         return n + (2 * U * U + U if self.type == "con" else 0)
-
-    @property
-    def learning_rate(self):
-        return self._lr
-
-    @learning_rate.setter
-    def learning_rate(self, lr):
-        self._lr = float(lr)
-        st = self.read_state()
-        st.lr = self._lr
-        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
-
-    def read_state(self):
-        return _hip.StepState.from_buffer_copy(self.state.cpu().numpy().tobytes())
-
-    @property
-    def loss_kind(self) -> int:
-        return loss_kind_of(self.loss, self.bce_on)
-
-    def set_article_matrix(self, matrix) -> None:
-        """Keep the loader's (n_articles+1, T) token matrix in HBM: batches can then be given as article-row numbers."""
-        m = np.asarray(matrix)
-        if m.ndim != 2 or m.shape[1] != self.T or not np.issubdtype(m.dtype, np.integer):
-            raise ValueError(f"article matrix must be integer (n_articles+1, {self.T}), got {m.dtype} {m.shape}")
-        if m.size and (m.min() < 0 or m.max() >= self.V):
-            raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-        self.article_matrix = torch.from_numpy(np.ascontiguousarray(m.astype(np.int32))).to(self.device)
-        self._article_matrix_src = matrix
 
     # ------------------------------------------------------------------ kernels
     def _encode(self, b: _Bufs, train: bool, expand=None):
@@ -315,110 +260,16 @@ class LSTUREngine:
              R, A, 0, S())
         call("ebn_gemm_f32_ws", 1, 0, F, A, R, f1, pt(b.Vd), F, pt(b.Ua), A, f0, pt(P.g("att_W")), A, ws, wsn, S())
         call("ebn_gemm_f32", 0, 1, R, F, A, f1, pt(b.Ua), A, pt(P.view("att_W")), A, f1, pt(b.dVd), F, S())
-        Wb = P.view("conv_Wb")
-        pc, pp = ctypes.c_float(self.p), ctypes.c_float(0.0)
-        call("ebn_conv1d_bwd_weight_f32", pt(b.X), pt(b.dVd), pt(b.Vd), pt(b.wpart), b.splits, N, T, E, F, self.window, st, pc, pp,
-             S())
-        job = (_hip.FinishJob * 1)()
-        job[0].kind, job[0].n_parts, job[0].rows, job[0].cols = _hip.FINISH_SPLITK, b.splits, self.window * E + 1, F
-        job[0].partials, job[0].out0, job[0].ld, job[0].beta, job[0].scale = b.wpart.data_ptr(), P.g("conv_Wb").data_ptr(), F, 0.0, 1.0
-        call("ebn_grad_finish_f32", job, 1, S())
-        if self.train_embedding:
-            call("ebn_conv1d_bwd_data_f32", pt(b.dVd), pt(b.Vd), pt(Wb), pt(b.dX), N, T, E, F, self.window, st, pc, pp, S())
-            call("ebn_embedding_grad_scatter_fixed", pt(b.ids), pt(b.dX), pt(self.table_acc), R, E, self.V, st,
-                 SITE_NEWS_IN if self.p > 0 else -1, pc, pt(self.range_flag), S())
+        self._conv_backward(ConvView(b.ids, b.X, b.Vd, b.dVd, b.dX, b.wpart, b.splits, T, "conv_Wb", SITE_NEWS_IN), N, self.p, 0.0)
         call("ebn_embedding_grad_scatter_fixed", pt(b.uidx), pt(b.dEu), pt(self.user_acc), B, U, self.n_users + 1, None, -1, f0,
              pt(self.range_flag), S())
 
-    def _optimizer_kernels(self):
-        """Keras Adam (nrms.py:69-80 form): dense parameters, then both tables straight from their fixed-point accumulators."""
-        S = _hip.stream_handle
-        call, pt = _hip.call, _hip.ptr
-        P = self.params
-        st = pt(self.state)
-        f1 = ctypes.c_float(1.0)
-        call("ebn_adam_keras_step_f32", pt(P.data), pt(P.grad), pt(P.m), pt(P.v), P.numel, st, BETA1, BETA2, ADAM_EPS, f1, S())
-        if self.train_embedding:
-            call("ebn_adam_keras_step_fixed_f32", pt(self.table), pt(self.table_acc), pt(self.table_m), pt(self.table_v),
-                 self.table.numel(), st, BETA1, BETA2, ADAM_EPS, f1, pt(self.range_flag), S())
-        call("ebn_adam_keras_step_fixed_f32", pt(self.user_table), pt(self.user_acc), pt(self.user_m), pt(self.user_v),
-             self.user_table.numel(), st, BETA1, BETA2, ADAM_EPS, f1, pt(self.range_flag), S())
+    # ------------------------------------------------------------------ hooks of the shared host entry points
+    def _new_bufs(self, B, n_cand, cand_imp, train):
+        return _Bufs(self, B, n_cand, train)
 
-    # ------------------------------------------------------------------ host entry points
-    def _uidx(self, user):
-        u = user if isinstance(user, torch.Tensor) else np.asarray(user)
-        return u.reshape(-1)
-
-    def _check(self, user, his):
-        if his.ndim != 3 or his.shape[1] != self.H or his.shape[2] != self.T:
-            raise ValueError(f"his_input_title must be (B, {self.H}, {self.T}), got {tuple(his.shape)}")
-        if user.shape[0] != his.shape[0]:
-            raise ValueError(f"user_indexes must hold one id per impression: {tuple(user.shape)} vs {tuple(his.shape)}")
-
-    def _host_ranges(self, user, *tok):
-        if not isinstance(user, torch.Tensor) and user.size and (user.min() < 0 or user.max() > self.n_users):
-            raise IndexError(f"user index out of range [0, {self.n_users}] for the user embedding table")
-        for a in tok:
-            if not isinstance(a, torch.Tensor) and a.size and (a.min() < 0 or a.max() >= self.V):
-                raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-
-    def _put(self, dst: torch.Tensor, src, dtype=torch.int32):
-        t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(src)))
-        dst.copy_(t.reshape(-1).to(device=self.device, dtype=dtype), non_blocking=True)
-
-    def _infer(self, user, his, cands):
-        """Inference-mode encoders: (user vectors (b, U), candidate news vectors (n, F))."""
-        user, his = self._uidx(user), his if isinstance(his, torch.Tensor) else np.asarray(his)
-        cands = cands if isinstance(cands, torch.Tensor) else np.asarray(cands)
-        self._check(user, his)
-        self._host_ranges(user, his, cands)
-        B, n = his.shape[0], cands.shape[0]
-        b = _Bufs(self, B, n, train=False)
-        self._put(b.ids[: B * self.H * self.T], his)
-        self._put(b.ids[B * self.H * self.T:], cands)
-        self._put(b.uidx, user)
-        self._encode(b, False)
-        self._check_oob()
-        return self._user_vec(b), b.NV[B * self.H:]
-
-    def forward(self, user, his, pred, mode="softmax"):
-        """(B,1) users, (B,H,T), (B,C,T) ids -> (probs (B,C), scores (B,C)) device tensors, inference mode."""
-        pred = pred if isinstance(pred, torch.Tensor) else np.asarray(pred)
-        if pred.ndim != 3 or pred.shape[2] != self.T:
-            raise ValueError(f"pred_input_title must be (B, C, {self.T}), got {tuple(pred.shape)}")
-        B, C = pred.shape[0], pred.shape[1]
-        user_vec, cand = self._infer(user, his, pred.reshape(B * C, self.T))
-        scores, probs = torch.empty(B, C, device=self.device), torch.empty(B, C, device=self.device)
-        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(probs), B, C, self.F,
-                  0 if mode == "softmax" else 1, _hip.stream_handle())
-        return probs, scores
-
-    def eval_loss(self, user, his, pred, y):
-        """Inference-mode forward + the compiled loss: (loss[1], probs (B,C))."""
-        pred = np.asarray(pred) if not isinstance(pred, torch.Tensor) else pred
-        B, C = pred.shape[0], pred.shape[1]
-        user_vec, cand = self._infer(user, his, pred.reshape(B * C, self.T))
-        scores, probs = torch.empty(B, C, device=self.device), torch.empty(B, C, device=self.device)
-        S = _hip.stream_handle
-        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(probs), B, C, self.F, 0, S())
-        labels = torch.as_tensor(np.ascontiguousarray(np.asarray(y, dtype=np.float32))).to(self.device).reshape(B, C).contiguous()
-        rows, junk_c, junk_u = torch.empty(B, device=self.device), torch.empty(B * C, self.F, device=self.device), torch.empty(B, self.F, device=self.device)
-        loss = torch.empty(1, device=self.device)
-        _hip.call("ebn_score_loss_bwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(labels), _hip.ptr(rows),
-                  _hip.ptr(junk_c), _hip.ptr(junk_u), B, C, self.F, self.loss_kind, ctypes.c_float(1.0 / B), S())
-        _hip.call("ebn_sum_f32", _hip.ptr(rows), B, ctypes.c_float(1.0), _hip.ptr(loss), 0, S())
-        return loss, probs
-
-    def pair_scores(self, user, his, cands, cand_imp, sigmoid=True):
-        """act(cand_i . user[cand_imp[i]]) for candidates (n, T) of impressions (user (b,), his (b,H,T)) -- scorer.predict."""
-        user_vec, cand = self._infer(user, his, cands)
-        n = cand.shape[0]
-        out = torch.empty(n, device=self.device)
-        ui = torch.from_numpy(np.ascontiguousarray(cand_imp, dtype=np.int32)).to(self.device)
-        ni = torch.arange(n, dtype=torch.int32, device=self.device)
-        _hip.call("ebn_pair_score_f32", _hip.ptr(user_vec), _hip.ptr(cand), _hip.ptr(ui), _hip.ptr(ni), _hip.ptr(out), n, self.F,
-                  1 if sigmoid else 0, _hip.stream_handle())
-        return out
+    def _graph_key_extra(self):
+        return (self.type,)
 
     # ------------------------------------------------------------------ scoring from a once-encoded catalogue
     def encode_catalogue(self, tokens, chunk=8192):
@@ -493,89 +344,9 @@ class LSTUREngine:
         cand_idx = np.asarray(cand_idx).reshape(-1)
         if cand_idx.size and (cand_idx.min() < 0 or cand_idx.max() >= cache.n_rows):
             raise IndexError(f"article row out of range [0, {cache.n_rows}) for the encoded catalogue")
-        n = cand_idx.shape[0]
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
         user_vec = self._user_vectors_indexed(cache, user, his_idx)
         ci, ui = i32(cand_idx), i32(np.asarray(cand_imp).reshape(-1))
-        out = torch.empty(n, device=self.device)
-        _hip.call("ebn_pair_score_f32", _hip.ptr(user_vec), _hip.ptr(cache.news_all), _hip.ptr(ui), _hip.ptr(ci), _hip.ptr(out), n,
-                  self.F, 1 if sigmoid else 0, _hip.stream_handle())
+        out = pair_score_tail(user_vec, cache.news_all, ui, ci, self.F, sigmoid)
         self._check_oob()
         return out
-
-    def _check_oob(self):
-        flags = torch.cat([self.oob_flag, self.user_oob_flag, self.range_flag, self.row_oob_flag])
-        oob, uoob, rng_bad, row_bad = (int(v) for v in flags.cpu().tolist())
-        if oob or uoob or rng_bad or row_bad:
-            self.oob_flag.zero_()
-            self.user_oob_flag.zero_()
-            self.range_flag.zero_()
-            self.row_oob_flag.zero_()
-        if row_bad:
-            raise IndexError("article row out of range for the encoded catalogue")
-        if uoob:
-            raise IndexError(f"user index out of range [0, {self.n_users}] for the user embedding table")
-        if oob:
-            raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-        if rng_bad:
-            raise FloatingPointError("embedding gradient left the range of the deterministic fixed-point accumulator: the run has "
-                                     "diverged")
-
-    def check_oob(self):
-        """One host read of the device flags (fit() calls it once per epoch): ids outside a table raise IndexError."""
-        self._check_oob()
-
-    def train_step(self, user, his, pred, y, return_probs=False, indexed=False):
-        """One optimizer step; returns the batch loss as a 1-element device tensor (no host sync).  The launch sequence of a
-        (B, C) shape is captured once into one hipGraph on the current stream and replayed (step-dependent scalars live in
-        the device step state).  indexed: his (B,H) / pred (B,C) are article-row numbers of set_article_matrix()'s matrix."""
-        user = self._uidx(user)
-        his = his if isinstance(his, torch.Tensor) else np.asarray(his)
-        pred = pred if isinstance(pred, torch.Tensor) else np.asarray(pred)
-        B, C = his.shape[0], pred.shape[1]
-        if user.shape[0] != B or pred.shape[0] != B:
-            raise ValueError(f"batch sizes differ: user {tuple(user.shape)}, his {tuple(his.shape)}, pred {tuple(pred.shape)}")
-        if indexed:
-            if self.article_matrix is None:
-                raise ValueError("indexed batches need set_article_matrix() first")
-            if his.ndim != 2 or his.shape[1] != self.H or pred.ndim != 2:
-                raise ValueError(f"indexed batches must be (B, {self.H}) and (B, C), got {tuple(his.shape)} {tuple(pred.shape)}")
-            self._host_ranges(user)
-        else:
-            self._check(user, his)
-            if pred.ndim != 3 or pred.shape[2] != self.T:
-                raise ValueError(f"pred_input_title must be (B, C, {self.T}), got {tuple(pred.shape)}")
-            self._host_ranges(user, his, pred)
-        b, expand = self._stage(user, his, pred, y, indexed)
-        key = (B, C, bool(indexed), self.type, self.loss_kind, self.train_embedding)
-        if self.use_graph:
-            g = self._graphs.get(key)
-            if g is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with _hip.capture(g):
-                    self._train_kernels(b, C, expand)
-                self._graphs[key] = g
-            g.replay()
-        else:
-            self._train_kernels(b, C, expand)
-        if return_probs:
-            return self.loss_dev, b.probs.view(B, C), b.labels.view(B, C)
-        return self.loss_dev
-
-    def _stage(self, user, his, pred, y, indexed):
-        """The step's static buffers for (B, C), filled with the batch: (buffers, article rows to expand or None)."""
-        B, C = his.shape[0], pred.shape[1]
-        b = self._bufs.get((B, C))
-        if b is None:
-            b = self._bufs[(B, C)] = _Bufs(self, B, B * C, train=True)
-            b.art = torch.empty(b.N, dtype=torch.int32, device=self.device)
-        if indexed:
-            self._put(b.art[: B * self.H], his)
-            self._put(b.art[B * self.H:], pred)
-        else:
-            self._put(b.ids[: B * self.H * self.T], his)
-            self._put(b.ids[B * self.H * self.T:], pred)
-        self._put(b.uidx, user)
-        self._put(b.labels, y, torch.float32)
-        return b, (b.art if indexed else None)

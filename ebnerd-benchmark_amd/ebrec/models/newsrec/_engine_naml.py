@@ -18,6 +18,11 @@ Data layout in HBM (fp32 row-major):
                               -> one Adam launch per step (the two small tables included: Keras' dense Adam on an Embedding)
   articles   N = B*(H+C) per step, history first (b*H + h), then candidates (B*H + b*C + c)
   views      Vw (4, N, F) view-major: the title / body poolings write Vw[0] / Vw[1] contiguously, the view x.W is one GEMM
+
+Shared with the other engines and defined in _engine_base.py (ConvEngineBase): constructor scaffolding, step state, the flag read
+(_check_oob over this engine's FLAGS), capture-or-replay of a step, the Adam launches, the Conv1D weight-gradient / finishing block and
+the eval_loss / pair_scores launch tails.  Here: buffers, shapes, weight order, the encoders, the backward, staging of the eight input
+arrays, and scoring from an encoded catalogue.
 """
 from __future__ import annotations
 
@@ -29,8 +34,8 @@ import torch
 
 from ebrec import _hip
 
-from ._engine import ADAM_EPS, BETA1, BETA2, FlatParams, glorot_uniform_np, loss_kind_of, require_gpu
-from ._engine_npa import conv_glorot_np
+from ._engine_base import (BETA1, BETA2, RANGE_FLAG, ROW_FLAG, TOKEN_FLAG, ConvEngineBase, ConvView, glorot_uniform_np, pair_score_tail,
+                           score_loss_tail)
 
 SITE_TITLE_IN, SITE_TITLE_CONV, SITE_BODY_IN, SITE_BODY_CONV = 0, 2, 5, 6
 N_VIEWS = 4
@@ -80,17 +85,17 @@ class _Bufs:
                             int(wsf(Rt, F, A)), int(wsf(Rb, F, A)), int(wsf(BH, F, A)), int(wsf(N_VIEWS * N, F, A)), 1))
 
 
-class NAMLEngine:
+class NAMLEngine(ConvEngineBase):
+    MODEL = "NAML"
+    FLAGS = (ROW_FLAG, TOKEN_FLAG, ("cat_oob_flag", IndexError, "category id out of range: vert ids must lie in [0, {e.n_vert}), "
+                                    "subvert ids in [0, {e.n_sub})"), RANGE_FLAG)
+
     def __init__(self, table: np.ndarray, title_size: int, body_size: int, history_size: int, filter_num: int, window_size: int,
                  attention_hidden_dim: int, vert_num: int, vert_emb_dim: int, subvert_num: int, subvert_emb_dim: int,
                  dropout: float, learning_rate: float, loss: str, seed=None, train_embedding: bool = True, device=None,
                  process_group=None, bce_on: str = "logits"):
-        if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
-            raise ValueError("NAMLModel runs on one rank: multi-rank NAML is not implemented (build it without a process group "
-                             "of more than one rank)")
-        self.device = require_gpu() if device is None else torch.device(device)
-        table = np.asarray(table, dtype=np.float32)
-        self.V, self.E = table.shape
+        self._require_one_rank(process_group)
+        self._init_table(table, device)
         self.T, self.Tb, self.H = int(title_size), int(body_size), int(history_size)
         self.F, self.A, self.window = int(filter_num), int(attention_hidden_dim), int(window_size)
         self.n_vert, self.Kv, self.n_sub, self.Ks = int(vert_num), int(vert_emb_dim), int(subvert_num), int(subvert_emb_dim)
@@ -100,44 +105,23 @@ class NAMLEngine:
         if min(self.n_vert, self.n_sub, self.Kv, self.Ks) < 1 or max(self.Kv, self.Ks) > 256:
             raise ValueError(f"vert/subvert tables must be non-empty with an embedding width in [1, 256], got "
                              f"({self.n_vert}, {self.Kv}) and ({self.n_sub}, {self.Ks})")
-        self.p = float(dropout)
-        self.loss, self.bce_on = loss, bce_on
-        loss_kind_of(loss, bce_on)
-        self.train_embedding = bool(train_embedding)
-        self.seed = seed
-        dev = self.device
         W, E, F, A = self.window, self.E, self.F, self.A
         shapes = {"t_conv": (W * E + 1, F), "t_aW": (F, A), "t_ab": (A,), "t_aq": (A,),
                   "b_conv": (W * E + 1, F), "b_aW": (F, A), "b_ab": (A,), "b_aq": (A,),
                   "v_emb": (self.n_vert, self.Kv), "v_Wb": (self.Kv + 1, F), "s_emb": (self.n_sub, self.Ks), "s_Wb": (self.Ks + 1, F),
                   "va_W": (F, A), "va_b": (A,), "va_q": (A,), "u_W": (F, A), "u_b": (A,), "u_q": (A,)}
-        self.params = FlatParams(shapes, dev)
-        self.table = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
-        self.table_acc = torch.zeros(self.table.numel(), dtype=torch.int64, device=dev)
-        self.table_m, self.table_v = torch.zeros_like(self.table), torch.zeros_like(self.table)
-        self.oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.cat_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.row_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)  # a row number outside an encoded catalogue
-        self.loss_dev = torch.zeros(1, device=dev)
-        st = _hip.StepState()
-        st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
-        self.state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev)
-        self._lr = float(learning_rate)
-        self._bufs, self._graphs = {}, {}
-        self.use_graph = True
+        self._init_state(shapes, dropout, learning_rate, loss, seed, train_embedding, bce_on)
         self.fuse_user_head = True  # False: the user pooling + loss as separate launches (validation of the fused head)
         self._init_weights(seed)
 
     # ------------------------------------------------------------------ parameters
     def _init_weights(self, seed):
         pv = self.params.view
-        W, E, F, A = self.window, self.E, self.F, self.A
+        F, A = self.F, self.A
         rng = np.random.default_rng(seed)
+        for conv in ("t_conv", "b_conv"):
+            self._conv_init(conv, seed)
         with torch.no_grad():
-            for conv in ("t_conv", "b_conv"):
-                pv(conv)[: W * E].copy_(torch.from_numpy(conv_glorot_np(W, E, F, seed).reshape(W * E, F)))
-                pv(conv)[W * E].zero_()
             for aW, ab, aq in _ATT.values():
                 pv(aW).copy_(torch.from_numpy(glorot_uniform_np((F, A), seed)))
                 pv(ab).zero_()
@@ -193,24 +177,6 @@ class NAMLEngine:
         return (self.table.numel() + 2 * (W * E * F + F) + 4 * (F * A + 2 * A) + self.n_vert * self.Kv + self.n_sub * self.Ks
                 + (self.Kv + self.Ks) * F + 2 * F)
 
-    @property
-    def learning_rate(self):
-        return self._lr
-
-    @learning_rate.setter
-    def learning_rate(self, lr):
-        self._lr = float(lr)
-        st = self.read_state()
-        st.lr = self._lr
-        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
-
-    def read_state(self):
-        return _hip.StepState.from_buffer_copy(self.state.cpu().numpy().tobytes())
-
-    @property
-    def loss_kind(self) -> int:
-        return loss_kind_of(self.loss, self.bce_on)
-
     # ------------------------------------------------------------------ kernels
     def _encode(self, b: _Bufs, train: bool, user: bool = True):
         """Forward of every article of the buffers' batch (ids already staged); training: dropout on.  user: also the user
@@ -265,7 +231,7 @@ class NAMLEngine:
         call, pt = _hip.call, _hip.ptr
         P, g = self.params, self.params.g
         st = pt(self.state)
-        B, N, E, F, A, H, W = b.B, b.N, self.E, self.F, self.A, self.H, self.window
+        B, N, F, A, H = b.B, b.N, self.F, self.A, self.H
         BH = B * H
         f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
         ws, wsn = pt(b.ws), b.ws.numel()
@@ -301,40 +267,18 @@ class NAMLEngine:
              pt(b.dVw[2]), pt(g("v_Wb")), pt(g("v_emb")), pt(b.cat_s), pt(P.view("s_emb")), self.n_sub, self.Ks, pt(P.view("s_Wb")),
              pt(b.Vw[3]), pt(b.dVw[3]), pt(g("s_Wb")), pt(g("s_emb")), pt(b.cpart), b.cpart.numel(), N, F, S())
         # title and body: AttLayer2 backward, then the Conv1D
-        pc, pp = ctypes.c_float(self.p), ctypes.c_float(0.0)
-        jobs = (_hip.FinishJob * 2)()
-        views = ((b.ids_t, b.Xt, b.Vt, b.Ut, b.wt, b.dVt, b.det, b.dXt, self.T, "t_conv", _ATT["t"], SITE_TITLE_IN, b.wpart_t,
-                  b.splits_t, 0),
-                 (b.ids_b, b.Xb, b.Vb, b.Ub, b.wb, b.dVb, b.deb, b.dXb, self.Tb, "b_conv", _ATT["b"], SITE_BODY_IN, b.wpart_b,
-                  b.splits_b, 1))
-        for ids, X, Vd, U, w, dVd, de, dX, L, conv, (aW, ab, aq), s_in, wpart, splits, v in views:
-            R = N * L
-            call("ebn_attpool_bwd_pool_f32", pt(Vd), pt(w), pt(b.dVw[v]), None, pt(de), N, L, F, S())
+        views = ((ConvView(b.ids_t, b.Xt, b.Vt, b.dVt, b.dXt, b.wpart_t, b.splits_t, self.T, "t_conv", SITE_TITLE_IN), b.Ut, b.wt, b.det,
+                  _ATT["t"], 0),
+                 (ConvView(b.ids_b, b.Xb, b.Vb, b.dVb, b.dXb, b.wpart_b, b.splits_b, self.Tb, "b_conv", SITE_BODY_IN), b.Ub, b.wb, b.deb,
+                  _ATT["b"], 1))
+        for cv, U, w, de, (aW, ab, aq), v in views:
+            R = N * cv.L
+            call("ebn_attpool_bwd_pool_f32", pt(cv.Vd), pt(w), pt(b.dVw[v]), None, pt(de), N, cv.L, F, S())
             call("ebn_attpool_bwd_dpre_f32", pt(U), pt(P.view(aq)), pt(de), pt(g(aq)), pt(g(ab)), pt(b.part), R, A, 0, S())
-            call("ebn_gemm_f32_ws", 1, 0, F, A, R, f1, pt(Vd), F, pt(U), A, f0, pt(g(aW)), A, ws, wsn, S())
-            call("ebn_gemm_f32_rank1", R, F, A, f1, pt(U), A, pt(P.view(aW)), A, pt(dVd), F, pt(w), pt(b.dVw[v]), F, L, ws, wsn, S())
-            call("ebn_conv1d_bwd_weight_f32", pt(X), pt(dVd), pt(Vd), pt(wpart), splits, N, L, E, F, W, st, pc, pp, S())
-            j = jobs[v]
-            j.kind, j.n_parts, j.rows, j.cols = _hip.FINISH_SPLITK, splits, W * E + 1, F
-            j.partials, j.out0, j.ld, j.beta, j.scale = wpart.data_ptr(), g(conv).data_ptr(), F, 0.0, 1.0
-        call("ebn_grad_finish_f32", jobs, 2, S())
-        if self.train_embedding:
-            for ids, X, Vd, U, w, dVd, de, dX, L, conv, _att, s_in, _wp, _sp, _v in views:
-                call("ebn_conv1d_bwd_data_f32", pt(dVd), pt(Vd), pt(P.view(conv)), pt(dX), N, L, E, F, W, st, pc, pp, S())
-                call("ebn_embedding_grad_scatter_fixed", pt(ids), pt(dX), pt(self.table_acc), N * L, E, self.V, st,
-                     s_in if self.p > 0 else -1, pc, pt(self.range_flag), S())
-
-    def _optimizer_kernels(self):
-        """Keras Adam (nrms.py:69-80 form): the dense buffer, then the word table straight from its fixed-point accumulator."""
-        S = _hip.stream_handle
-        call, pt = _hip.call, _hip.ptr
-        P = self.params
-        st = pt(self.state)
-        f1 = ctypes.c_float(1.0)
-        call("ebn_adam_keras_step_f32", pt(P.data), pt(P.grad), pt(P.m), pt(P.v), P.numel, st, BETA1, BETA2, ADAM_EPS, f1, S())
-        if self.train_embedding:
-            call("ebn_adam_keras_step_fixed_f32", pt(self.table), pt(self.table_acc), pt(self.table_m), pt(self.table_v),
-                 self.table.numel(), st, BETA1, BETA2, ADAM_EPS, f1, pt(self.range_flag), S())
+            call("ebn_gemm_f32_ws", 1, 0, F, A, R, f1, pt(cv.Vd), F, pt(U), A, f0, pt(g(aW)), A, ws, wsn, S())
+            call("ebn_gemm_f32_rank1", R, F, A, f1, pt(U), A, pt(P.view(aW)), A, pt(cv.dVd), F, pt(w), pt(b.dVw[v]), F, cv.L, ws, wsn, S())
+            self._conv_wgrad(cv, N, self.p, 0.0)
+        self._conv_finish([view[0] for view in views], N, self.p, 0.0)  # both weight gradients in one finishing launch
 
     # ------------------------------------------------------------------ host entry points
     def _arrays(self, xs, what):
@@ -352,10 +296,6 @@ class NAMLEngine:
             if not isinstance(a, torch.Tensor) and a.size and (a.min() < 0 or a.max() >= self.V):
                 raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
         return t, bo, v, s
-
-    def _put(self, dst: torch.Tensor, src, dtype=torch.int32):
-        t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(src)))
-        dst.copy_(t.reshape(-1).to(device=self.device, dtype=dtype), non_blocking=True)
 
     def _fill(self, b: _Bufs, his, cands):
         """Stage the token and category ids: history articles first, then the candidates."""
@@ -393,16 +333,7 @@ class NAMLEngine:
         y = xs[8]
         B, C = np.shape(xs[4])[:2]
         user_vec, cand = self._infer(xs[:4], xs[4:8], None)
-        scores, probs = torch.empty(B, C, device=self.device), torch.empty(B, C, device=self.device)
-        S = _hip.stream_handle
-        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(probs), B, C, self.F, 0, S())
-        labels = torch.as_tensor(np.ascontiguousarray(np.asarray(y, dtype=np.float32))).to(self.device).reshape(B, C).contiguous()
-        rows, junk_c, junk_u = torch.empty(B, device=self.device), torch.empty(B * C, self.F, device=self.device), torch.empty(B, self.F, device=self.device)
-        loss = torch.empty(1, device=self.device)
-        _hip.call("ebn_score_loss_bwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(labels), _hip.ptr(rows),
-                  _hip.ptr(junk_c), _hip.ptr(junk_u), B, C, self.F, self.loss_kind, ctypes.c_float(1.0 / B), S())
-        _hip.call("ebn_sum_f32", _hip.ptr(rows), B, ctypes.c_float(1.0), _hip.ptr(loss), 0, S())
-        return loss, probs
+        return score_loss_tail(cand, user_vec, y, B, C, self.F, self.loss_kind)[:2]
 
     def pair_scores(self, his, cands, cand_imp, sigmoid=True):
         """act(cand_i . user[cand_imp[i]]) for the candidates (title (n,T), body (n,Tb), vert (n,), subvert (n,)) of the impressions
@@ -411,12 +342,9 @@ class NAMLEngine:
         n = cands[0].shape[0]
         cands = (cands[0].reshape(n, 1, self.T), cands[1].reshape(n, 1, self.Tb), cands[2].reshape(n, 1, 1), cands[3].reshape(n, 1, 1))
         user_vec, cand = self._infer(his, cands, cand_imp)
-        out = torch.empty(n, device=self.device)
         ui = torch.from_numpy(np.ascontiguousarray(cand_imp, dtype=np.int32)).to(self.device)
         ni = torch.arange(n, dtype=torch.int32, device=self.device)
-        _hip.call("ebn_pair_score_f32", _hip.ptr(user_vec), _hip.ptr(cand), _hip.ptr(ui), _hip.ptr(ni), _hip.ptr(out), n, self.F,
-                  1 if sigmoid else 0, _hip.stream_handle())
-        return out
+        return pair_score_tail(user_vec, cand, ui, ni, self.F, sigmoid)
 
     # ------------------------------------------------------------------ scoring from a once-encoded catalogue
     def encode_catalogue(self, title, body, vert, subvert, chunk=4096):
@@ -471,28 +399,6 @@ class NAMLEngine:
         self._check_oob()
         return (out, user) if return_user else out
 
-    def _check_oob(self):
-        flags = torch.cat([self.oob_flag, self.cat_oob_flag, self.range_flag, self.row_oob_flag])
-        oob, coob, rng_bad, row_bad = (int(v) for v in flags.cpu().tolist())
-        if oob or coob or rng_bad or row_bad:
-            self.oob_flag.zero_()
-            self.cat_oob_flag.zero_()
-            self.range_flag.zero_()
-            self.row_oob_flag.zero_()
-        if row_bad:
-            raise IndexError("article row out of range for the encoded catalogue")
-        if oob:
-            raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-        if coob:
-            raise IndexError(f"category id out of range: vert ids must lie in [0, {self.n_vert}), subvert ids in [0, {self.n_sub})")
-        if rng_bad:
-            raise FloatingPointError("embedding gradient left the range of the deterministic fixed-point accumulator: the run has "
-                                     "diverged")
-
-    def check_oob(self):
-        """One host read of the device flags (fit() calls it once per epoch): ids outside a table raise IndexError."""
-        self._check_oob()
-
     def train_step(self, *xs, return_probs=False):
         """One optimizer step on (the 8 input arrays, y); returns the batch loss as a 1-element device tensor (no host sync).  The
         launch sequence of a (B, C) shape is captured once into one hipGraph on the current stream (one stream, no parallel
@@ -505,17 +411,7 @@ class NAMLEngine:
             raise ValueError(f"his_input_title must be ({B}, {self.H}, {self.T}), got {tuple(his[0].shape)}")
         b = self._stage(his, pred, y)
         key = (B, C, self.loss_kind, self.train_embedding, self.fuse_user_head)
-        if self.use_graph:
-            g = self._graphs.get(key)
-            if g is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with _hip.capture(g):
-                    self._train_kernels(b, C)
-                self._graphs[key] = g
-            g.replay()
-        else:
-            self._train_kernels(b, C)
+        self._run_step(key, lambda: self._train_kernels(b, C))
         if return_probs:
             return self.loss_dev, b.probs.view(B, C), b.labels.view(B, C)
         return self.loss_dev

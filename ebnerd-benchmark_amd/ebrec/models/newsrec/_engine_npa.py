@@ -15,11 +15,14 @@ Data layout in HBM (fp32 row-major):
   dense        flat buffer         conv_Wb (window*E + 1, F) = Conv1D kernel rows | bias row, then n_Wa, n_ba, n_Wq, n_bq,
                                    u_Wa, u_ba, u_Wq, u_bq -> one Adam launch per step
   titles       N = B*(H+C) per step, history titles first (b*H + h), then candidates (B*H + b*C + c); q_idx[n] = impression
+
+Shared with the other engines and defined in _engine_base.py: constructor scaffolding, step state, flags (_check_oob), staging and
+train_step, forward / eval_loss / pair_scores, the Adam launches, the Conv1D backward block (UserTableEngine <- ConvEngineBase).  Here:
+buffers, shapes, weight order, the encoder, the backward up to the Conv1D, and scoring from an encoded catalogue.
 """
 from __future__ import annotations
 
 import ctypes
-import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -27,20 +30,13 @@ import torch
 
 from ebrec import _hip
 
-from ._engine import ADAM_EPS, BETA1, BETA2, FlatParams, glorot_uniform_np, loss_kind_of, require_gpu
+from ._engine_base import BETA1, BETA2, ConvView, UserTableEngine, glorot_uniform_np
 
 SITE_NEWS_IN, SITE_CONV, SITE_NEWS_PAP, SITE_USER_PAP = 0, 2, 3, 4
 PAP_DROPOUT = 0.2  # layers.py:324: a fixed rate, not hparams.dropout
 
 WEIGHT_NAMES = ["news.emb", "user.emb", "news.conv.W", "news.conv.b", "news.query.W", "news.query.b", "news.pap.W", "news.pap.b",
                 "user.query.W", "user.query.b", "user.pap.W", "user.pap.b"]
-
-
-def conv_glorot_np(window, E, F, seed):
-    """GlorotUniform of a Conv1D kernel (window, E, F): fan_in = window*E, fan_out = window*F (Keras' receptive-field rule)."""
-    rng = np.random.default_rng(seed)
-    lim = math.sqrt(6.0 / (window * E + window * F))
-    return rng.uniform(-lim, lim, size=(window, E, F)).astype(np.float32)
 
 
 class _Bufs:
@@ -75,57 +71,30 @@ class _Bufs:
                             int(wsf(B * H, F, A)), 1))
 
 
-class NPAEngine:
+class NPAEngine(UserTableEngine):
+    MODEL = "NPA"
+
     def __init__(self, table: np.ndarray, n_users: int, title_size: int, history_size: int, filter_num: int, window_size: int,
                  attention_hidden_dim: int, user_emb_dim: int, dropout: float, learning_rate: float, loss: str, seed=None,
                  train_embedding: bool = True, device=None, process_group=None, bce_on: str = "logits"):
-        if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
-            raise ValueError("NPAModel runs on one rank: multi-rank NPA is not implemented (build it without a process group "
-                             "of more than one rank)")
-        self.device = require_gpu() if device is None else torch.device(device)
-        table = np.asarray(table, dtype=np.float32)
-        self.V, self.E = table.shape
+        self._require_one_rank(process_group)
+        self._init_table(table, device)
         self.n_users, self.Du = int(n_users), int(user_emb_dim)
         self.T, self.H, self.F, self.A, self.window = int(title_size), int(history_size), int(filter_num), int(attention_hidden_dim), int(window_size)
         if self.E % 4 or self.F % 4:
             raise ValueError(f"word_emb_dim ({self.E}) and filter_num ({self.F}) must be multiples of 4 for the HIP Conv1D")
-        self.p = float(dropout)
-        self.loss, self.bce_on = loss, bce_on
-        loss_kind_of(loss, bce_on)
-        self.train_embedding = bool(train_embedding)
-        self.seed = seed
-        dev = self.device
         W, E, F, A, Du = self.window, self.E, self.F, self.A, self.Du
-        self.params = FlatParams({"conv_Wb": (W * E + 1, F), "n_Wa": (F, A), "n_ba": (A,), "n_Wq": (Du, A), "n_bq": (A,),
-                                  "u_Wa": (F, A), "u_ba": (A,), "u_Wq": (Du, A), "u_bq": (A,)}, dev)
-        self.table = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
-        self.user_table = torch.zeros(self.n_users + 1, Du, device=dev)  # embeddings_initializer="zeros" (npa.py:180-185)
-        self.table_acc = torch.zeros(self.table.numel(), dtype=torch.int64, device=dev)
-        self.table_m, self.table_v = torch.zeros_like(self.table), torch.zeros_like(self.table)
-        self.user_acc = torch.zeros(self.user_table.numel(), dtype=torch.int64, device=dev)
-        self.user_m, self.user_v = torch.zeros_like(self.user_table), torch.zeros_like(self.user_table)
-        self.oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.user_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.row_oob_flag = torch.zeros(1, dtype=torch.int32, device=dev)  # a row outside an encoded catalogue
-        self.loss_dev = torch.zeros(1, device=dev)
-        st = _hip.StepState()
-        st.step, st.seed, st.lr, st.adam_alpha = 0, (0 if seed is None else int(seed)) & 0xFFFFFFFF, learning_rate, 0.0
-        self.state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev)
-        self._lr = float(learning_rate)
-        self._bufs, self._graphs = {}, {}
-        self.use_graph = True
-        self.article_matrix = None
-        self._article_matrix_src = None
+        shapes = {"conv_Wb": (W * E + 1, F), "n_Wa": (F, A), "n_ba": (A,), "n_Wq": (Du, A), "n_bq": (A,),
+                  "u_Wa": (F, A), "u_ba": (A,), "u_Wq": (Du, A), "u_bq": (A,)}
+        self._init_state(shapes, Du, dropout, learning_rate, loss, seed, train_embedding, bce_on)  # user table: npa.py:180-185
         self._init_weights(seed)
 
     # ------------------------------------------------------------------ parameters
     def _init_weights(self, seed):
         pv = self.params.view
-        W, E, F, A, Du = self.window, self.E, self.F, self.A, self.Du
+        F, A, Du = self.F, self.A, self.Du
+        self._conv_init("conv_Wb", seed)
         with torch.no_grad():
-            pv("conv_Wb")[: W * E].copy_(torch.from_numpy(conv_glorot_np(W, E, F, seed).reshape(W * E, F)))
-            pv("conv_Wb")[W * E].zero_()
             for name, shape in (("n_Wa", (F, A)), ("n_Wq", (Du, A)), ("u_Wa", (F, A)), ("u_Wq", (Du, A))):
                 pv(name).copy_(torch.from_numpy(glorot_uniform_np(shape, seed)))
             for name in ("n_ba", "n_bq", "u_ba", "u_bq"):
@@ -136,10 +105,8 @@ class NPAEngine:
 
     def get_weights(self):
         pv = lambda n: self.params.view(n).cpu().numpy()
-        W, E, F = self.window, self.E, self.F
-        wb = pv("conv_Wb")
-        return [self.table.cpu().numpy(), self.user_table.cpu().numpy(), wb[: W * E].reshape(W, E, F).copy(), wb[W * E].copy(),
-                pv("n_Wq"), pv("n_bq"), pv("n_Wa"), pv("n_ba"), pv("u_Wq"), pv("u_bq"), pv("u_Wa"), pv("u_ba")]
+        return ([self.table.cpu().numpy(), self.user_table.cpu().numpy()] + self._conv_get("conv_Wb")
+                + [pv(n) for n in ("n_Wq", "n_bq", "n_Wa", "n_ba", "u_Wq", "u_bq", "u_Wa", "u_ba")])
 
     def set_weights(self, weights):
         if len(weights) != len(WEIGHT_NAMES):
@@ -155,42 +122,13 @@ class NPAEngine:
             self.table.copy_(t(w[0]))
             self.user_table.copy_(t(w[1]))
             pv = self.params.view
-            pv("conv_Wb")[: W * E].copy_(t(w[2].reshape(W * E, F)))
-            pv("conv_Wb")[W * E].copy_(t(w[3]))
+            self._conv_set("conv_Wb", w[2], w[3])
             for name, a in zip(("n_Wq", "n_bq", "n_Wa", "n_ba", "u_Wq", "u_bq", "u_Wa", "u_ba"), w[4:]):
                 pv(name).copy_(t(a.reshape(pv(name).shape)))
 
     def count_params(self):
         W, E, F, A, Du = self.window, self.E, self.F, self.A, self.Du
         return self.table.numel() + self.user_table.numel() + W * E * F + F + 2 * (F * A + A + Du * A + A)
-
-    @property
-    def learning_rate(self):
-        return self._lr
-
-    @learning_rate.setter
-    def learning_rate(self, lr):
-        self._lr = float(lr)
-        st = self.read_state()
-        st.lr = self._lr
-        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
-
-    def read_state(self):
-        return _hip.StepState.from_buffer_copy(self.state.cpu().numpy().tobytes())
-
-    @property
-    def loss_kind(self) -> int:
-        return loss_kind_of(self.loss, self.bce_on)
-
-    def set_article_matrix(self, matrix) -> None:
-        """Keep the loader's (n_articles+1, T) token matrix in HBM: batches can then be given as article-row numbers."""
-        m = np.asarray(matrix)
-        if m.ndim != 2 or m.shape[1] != self.T or not np.issubdtype(m.dtype, np.integer):
-            raise ValueError(f"article matrix must be integer (n_articles+1, {self.T}), got {m.dtype} {m.shape}")
-        if m.size and (m.min() < 0 or m.max() >= self.V):
-            raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-        self.article_matrix = torch.from_numpy(np.ascontiguousarray(m.astype(np.int32))).to(self.device)
-        self._article_matrix_src = matrix
 
     # ------------------------------------------------------------------ kernels
     def _encode(self, b: _Bufs, train: bool, expand=None):
@@ -240,7 +178,6 @@ class NPAEngine:
         st = pt(self.state)
         B, N, R, T, E, F, A, Du, H = b.B, b.N, b.R, self.T, self.E, self.F, self.A, self.Du, self.H
         f1, f0 = ctypes.c_float(1.0), ctypes.c_float(0.0)
-        p_in = self.p
         call("ebn_step_advance", st, BETA1, BETA2, S())
         self._encode(b, True, expand)
         cand = b.NV[B * H:]
@@ -263,19 +200,7 @@ class NPAEngine:
         call("ebn_gemm_f32_ws", 0, 0, 1, A, R, f1, pt(b.ones), R, pt(b.U), A, f0, pt(P.g("n_ba")), A, ws, wsn, S())
         call("ebn_gemm_f32_rank1", R, F, A, f1, pt(b.U), A, pt(P.view("n_Wa")), A, pt(b.dVd), F, pt(b.w), pt(b.dNV), F, T, ws, wsn,
              S())
-        Wb = P.view("conv_Wb")
-        pc = ctypes.c_float(p_in)
-        pp = ctypes.c_float(PAP_DROPOUT)
-        call("ebn_conv1d_bwd_weight_f32", pt(b.X), pt(b.dVd), pt(b.Vd), pt(b.wpart), b.splits, N, T, E, F, self.window, st, pc, pp,
-             S())
-        job = (_hip.FinishJob * 1)()
-        job[0].kind, job[0].n_parts, job[0].rows, job[0].cols = _hip.FINISH_SPLITK, b.splits, self.window * E + 1, F
-        job[0].partials, job[0].out0, job[0].ld, job[0].beta, job[0].scale = b.wpart.data_ptr(), P.g("conv_Wb").data_ptr(), F, 0.0, 1.0
-        call("ebn_grad_finish_f32", job, 1, S())
-        if self.train_embedding:
-            call("ebn_conv1d_bwd_data_f32", pt(b.dVd), pt(b.Vd), pt(Wb), pt(b.dX), N, T, E, F, self.window, st, pc, pp, S())
-            call("ebn_embedding_grad_scatter_fixed", pt(b.ids), pt(b.dX), pt(self.table_acc), R, E, self.V, st,
-                 SITE_NEWS_IN if p_in > 0 else -1, pc, pt(self.range_flag), S())
+        self._conv_backward(ConvView(b.ids, b.X, b.Vd, b.dVd, b.dX, b.wpart, b.splits, T, "conv_Wb", SITE_NEWS_IN), N, self.p, PAP_DROPOUT)
         # the two query Dense layers and the user embedding
         for dQ, Wq, bq in ((b.dQn, "n_Wq", "n_bq"), (b.dQu, "u_Wq", "u_bq")):
             call("ebn_gemm_f32", 1, 0, Du, A, B, f1, pt(b.Eu), Du, pt(dQ), A, f0, pt(P.g(Wq)), A, S())
@@ -285,96 +210,12 @@ class NPAEngine:
         call("ebn_embedding_grad_scatter_fixed", pt(b.uidx), pt(b.dEu), pt(self.user_acc), B, Du, self.n_users + 1, None, -1, f0,
              pt(self.range_flag), S())
 
-    def _optimizer_kernels(self):
-        """Keras Adam (nrms.py:69-80 form): dense parameters, then both tables straight from their fixed-point accumulators."""
-        S = _hip.stream_handle
-        call, pt = _hip.call, _hip.ptr
-        P = self.params
-        st = pt(self.state)
-        f1 = ctypes.c_float(1.0)
-        call("ebn_adam_keras_step_f32", pt(P.data), pt(P.grad), pt(P.m), pt(P.v), P.numel, st, BETA1, BETA2, ADAM_EPS, f1, S())
-        if self.train_embedding:
-            call("ebn_adam_keras_step_fixed_f32", pt(self.table), pt(self.table_acc), pt(self.table_m), pt(self.table_v),
-                 self.table.numel(), st, BETA1, BETA2, ADAM_EPS, f1, pt(self.range_flag), S())
-        call("ebn_adam_keras_step_fixed_f32", pt(self.user_table), pt(self.user_acc), pt(self.user_m), pt(self.user_v),
-             self.user_table.numel(), st, BETA1, BETA2, ADAM_EPS, f1, pt(self.range_flag), S())
+    # ------------------------------------------------------------------ hooks of the shared host entry points
+    def _new_bufs(self, B, n_cand, cand_imp, train):
+        return _Bufs(self, B, n_cand, cand_imp, train)
 
-    # ------------------------------------------------------------------ host entry points
-    def _uidx(self, user):
-        u = user if isinstance(user, torch.Tensor) else np.asarray(user)
-        return u.reshape(-1)
-
-    def _check(self, user, his, n_cand_rows=None):
-        if his.ndim != 3 or his.shape[1] != self.H or his.shape[2] != self.T:
-            raise ValueError(f"his_input_title must be (B, {self.H}, {self.T}), got {tuple(his.shape)}")
-        if user.shape[0] != his.shape[0]:
-            raise ValueError(f"user_indexes must hold one id per impression: {tuple(user.shape)} vs {tuple(his.shape)}")
-
-    def _host_ranges(self, user, *tok):
-        if not isinstance(user, torch.Tensor) and user.size and (user.min() < 0 or user.max() > self.n_users):
-            raise IndexError(f"user index out of range [0, {self.n_users}] for the user embedding table")
-        for a in tok:
-            if not isinstance(a, torch.Tensor) and a.size and (a.min() < 0 or a.max() >= self.V):
-                raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-
-    def _put(self, dst: torch.Tensor, src, dtype=torch.int32):
-        t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(src)))
-        dst.copy_(t.reshape(-1).to(device=self.device, dtype=dtype), non_blocking=True)
-
-    def _infer(self, user, his, cands, cand_imp):
-        """Inference-mode encoders: (user vectors (b, F), candidate news vectors (n, F)); candidate i uses impression
-        cand_imp[i]'s query."""
-        user, his = self._uidx(user), his if isinstance(his, torch.Tensor) else np.asarray(his)
-        cands = cands if isinstance(cands, torch.Tensor) else np.asarray(cands)
-        self._check(user, his)
-        self._host_ranges(user, his, cands)
-        B, n = his.shape[0], cands.shape[0]
-        b = _Bufs(self, B, n, np.asarray(cand_imp), train=False)
-        self._put(b.ids[: B * self.H * self.T], his)
-        self._put(b.ids[B * self.H * self.T:], cands)
-        self._put(b.uidx, user)
-        self._encode(b, False)
-        self._check_oob()
-        return b.user, b.NV[B * self.H:]
-
-    def forward(self, user, his, pred, mode="softmax"):
-        """(B,1) users, (B,H,T), (B,C,T) ids -> (probs (B,C), scores (B,C)) device tensors, inference mode."""
-        pred = pred if isinstance(pred, torch.Tensor) else np.asarray(pred)
-        if pred.ndim != 3 or pred.shape[2] != self.T:
-            raise ValueError(f"pred_input_title must be (B, C, {self.T}), got {tuple(pred.shape)}")
-        B, C = pred.shape[0], pred.shape[1]
-        user_vec, cand = self._infer(user, his, pred.reshape(B * C, self.T), np.repeat(np.arange(B), C))
-        scores, probs = torch.empty(B, C, device=self.device), torch.empty(B, C, device=self.device)
-        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(probs), B, C, self.F,
-                  0 if mode == "softmax" else 1, _hip.stream_handle())
-        return probs, scores
-
-    def eval_loss(self, user, his, pred, y):
-        """Inference-mode forward + the compiled loss: (loss[1], probs (B,C))."""
-        pred = np.asarray(pred) if not isinstance(pred, torch.Tensor) else pred
-        B, C = pred.shape[0], pred.shape[1]
-        user_vec, cand = self._infer(user, his, pred.reshape(B * C, self.T), np.repeat(np.arange(B), C))
-        scores, probs = torch.empty(B, C, device=self.device), torch.empty(B, C, device=self.device)
-        S = _hip.stream_handle
-        _hip.call("ebn_score_fwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(probs), B, C, self.F, 0, S())
-        labels = torch.as_tensor(np.ascontiguousarray(np.asarray(y, dtype=np.float32))).to(self.device).reshape(B, C).contiguous()
-        rows, junk_c, junk_u = torch.empty(B, device=self.device), torch.empty(B * C, self.F, device=self.device), torch.empty(B, self.F, device=self.device)
-        loss = torch.empty(1, device=self.device)
-        _hip.call("ebn_score_loss_bwd_f32", _hip.ptr(cand), _hip.ptr(user_vec), _hip.ptr(scores), _hip.ptr(labels), _hip.ptr(rows),
-                  _hip.ptr(junk_c), _hip.ptr(junk_u), B, C, self.F, self.loss_kind, ctypes.c_float(1.0 / B), S())
-        _hip.call("ebn_sum_f32", _hip.ptr(rows), B, ctypes.c_float(1.0), _hip.ptr(loss), 0, S())
-        return loss, probs
-
-    def pair_scores(self, user, his, cands, cand_imp, sigmoid=True):
-        """act(cand_i . user[cand_imp[i]]) for candidates (n, T) of impressions (user (b,), his (b,H,T)) -- scorer.predict."""
-        user_vec, cand = self._infer(user, his, cands, cand_imp)
-        n = cand.shape[0]
-        out = torch.empty(n, device=self.device)
-        ui = torch.from_numpy(np.ascontiguousarray(cand_imp, dtype=np.int32)).to(self.device)
-        ni = torch.arange(n, dtype=torch.int32, device=self.device)
-        _hip.call("ebn_pair_score_f32", _hip.ptr(user_vec), _hip.ptr(cand), _hip.ptr(ui), _hip.ptr(ni), _hip.ptr(out), n, self.F,
-                  1 if sigmoid else 0, _hip.stream_handle())
-        return out
+    def _user_vec(self, b: _Bufs):
+        return b.user
 
     # ------------------------------------------------------------------ scoring from a once-encoded catalogue
     def catalogue_bytes(self, n_rows) -> int:
@@ -476,80 +317,3 @@ class NPAEngine:
                  pt(out), 1 if sigmoid else 0, pt(self.row_oob_flag), n, self.T, self.F, self.A, _hip.stream_handle())
         self._check_oob()
         return out
-
-    def _check_oob(self):
-        flags = torch.cat([self.oob_flag, self.user_oob_flag, self.range_flag, self.row_oob_flag])
-        oob, uoob, rng_bad, row_bad = (int(v) for v in flags.cpu().tolist())
-        if oob or uoob or rng_bad or row_bad:
-            self.oob_flag.zero_()
-            self.user_oob_flag.zero_()
-            self.range_flag.zero_()
-            self.row_oob_flag.zero_()
-        if row_bad:
-            raise IndexError("article row out of range for the encoded catalogue")
-        if uoob:
-            raise IndexError(f"user index out of range [0, {self.n_users}] for the user embedding table")
-        if oob:
-            raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-        if rng_bad:
-            raise FloatingPointError("embedding gradient left the range of the deterministic fixed-point accumulator: the run has "
-                                     "diverged")
-
-    def check_oob(self):
-        """One host read of the device flags (fit() calls it once per epoch): ids outside a table raise IndexError."""
-        self._check_oob()
-
-    def train_step(self, user, his, pred, y, return_probs=False, indexed=False):
-        """One optimizer step; returns the batch loss as a 1-element device tensor (no host sync).  The launch sequence of a
-        (B, C) shape is captured once into one hipGraph on the current stream and replayed (step-dependent scalars live in
-        the device step state).  indexed: his (B,H) / pred (B,C) are article-row numbers of set_article_matrix()'s matrix."""
-        user = self._uidx(user)
-        his = his if isinstance(his, torch.Tensor) else np.asarray(his)
-        pred = pred if isinstance(pred, torch.Tensor) else np.asarray(pred)
-        B, C = his.shape[0], pred.shape[1]
-        if user.shape[0] != B or pred.shape[0] != B:
-            raise ValueError(f"batch sizes differ: user {tuple(user.shape)}, his {tuple(his.shape)}, pred {tuple(pred.shape)}")
-        if indexed:
-            if self.article_matrix is None:
-                raise ValueError("indexed batches need set_article_matrix() first")
-            if his.ndim != 2 or his.shape[1] != self.H or pred.ndim != 2:
-                raise ValueError(f"indexed batches must be (B, {self.H}) and (B, C), got {tuple(his.shape)} {tuple(pred.shape)}")
-            self._host_ranges(user)
-        else:
-            self._check(user, his)
-            if pred.ndim != 3 or pred.shape[2] != self.T:
-                raise ValueError(f"pred_input_title must be (B, C, {self.T}), got {tuple(pred.shape)}")
-            self._host_ranges(user, his, pred)
-        b, expand = self._stage(user, his, pred, y, indexed)
-        key = (B, C, bool(indexed), self.loss_kind, self.train_embedding)
-        if self.use_graph:
-            g = self._graphs.get(key)
-            if g is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with _hip.capture(g):
-                    self._train_kernels(b, C, expand)
-                self._graphs[key] = g
-            g.replay()
-        else:
-            self._train_kernels(b, C, expand)
-        if return_probs:
-            return self.loss_dev, b.probs.view(B, C), b.labels.view(B, C)
-        return self.loss_dev
-
-    def _stage(self, user, his, pred, y, indexed):
-        """The step's static buffers for (B, C), filled with the batch: (buffers, article rows to expand or None)."""
-        B, C = his.shape[0], pred.shape[1]
-        b = self._bufs.get((B, C))
-        if b is None:
-            b = self._bufs[(B, C)] = _Bufs(self, B, B * C, np.repeat(np.arange(B), C), train=True)
-            b.art = torch.empty(b.N, dtype=torch.int32, device=self.device)
-        if indexed:
-            self._put(b.art[: B * self.H], his)
-            self._put(b.art[B * self.H:], pred)
-        else:
-            self._put(b.ids[: B * self.H * self.T], his)
-            self._put(b.ids[B * self.H * self.T:], pred)
-        self._put(b.uidx, user)
-        self._put(b.labels, y, torch.float32)
-        return b, (b.art if indexed else None)

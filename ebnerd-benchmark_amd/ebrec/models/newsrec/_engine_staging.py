@@ -11,22 +11,15 @@ import torch
 
 from ebrec import _hip
 
+from ._engine_base import set_article_matrix
+
 BETA1, BETA2 = 0.9, 0.999  # tf.keras.optimizers.Adam defaults (nrms.py:77): the staging launch advances the step state
 
 
 class StagingMixin:
     # ------------------------------------------------------------------ training
     # ------------------------------------------------------------------ device-side batch assembly (a13)
-    def set_article_matrix(self, matrix) -> None:
-        """Keep the loader's (n_articles+1, T) token matrix in HBM; batches can then be given as article-row
-        numbers (``train_step(..., indexed=True)``) and expanded to token ids on the device."""
-        m = np.asarray(matrix)
-        if m.ndim != 2 or m.shape[1] != self.T or not np.issubdtype(m.dtype, np.integer):
-            raise ValueError(f"article matrix must be integer (n_articles+1, {self.T}), got {m.dtype} {m.shape}")
-        if m.size and (m.min() < 0 or m.max() >= self.V):
-            raise IndexError(f"token id out of range [0, {self.V}) for the embedding table")
-        self.article_matrix = torch.from_numpy(np.ascontiguousarray(m.astype(np.int32))).to(self.device)
-        self._article_matrix_src = matrix
+    set_article_matrix = set_article_matrix  # the one implementation of every token-matrix engine (_engine_base.py)
 
     def _stage_host(self, int_arrays, dst_int: torch.Tensor, y, dst_lab: torch.Tensor) -> None:
         """Host integers (token ids or article-row numbers) + labels -> device in ONE asynchronous copy out of a pinned,

@@ -13,7 +13,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from ._engine import eval_loss_from_news
+from ._engine import eval_loss_from_news, glorot_uniform_np
+from ._recommend import recommend
 from .callbacks import Callback, History, StreamingAUC
 
 
@@ -390,6 +391,49 @@ class ScorerModel:
 
     def __call__(self, inputs, training=False):
         return self._owner._score_pairs(*(np.asarray(a) for a in inputs)).view(-1, 1)
+
+
+class ModelBase:
+    """What the ``*Model`` classes share: the reference's constructor preface and helper names (nrms.py:23-80).  A subclass builds
+    its engine between ``_preface`` and ``_build_graph`` and supplies the scorer bodies and cache hooks."""
+
+    def _preface(self, hparams, seed, word2vec_embedding=None, word_emb_dim=None, vocab_size=None):
+        """Seeding, the Xavier fallback for a missing (vocab_size, word_emb_dim) word table (models that have one), and the
+        validation of loss and optimizer -- before the device is touched (same errors as nrms.py:56-80)."""
+        self.hparams = hparams
+        self.seed = seed
+        if seed is not None:
+            np.random.seed(seed)  # nrms.py:36-37 seeds the global generators
+            torch.manual_seed(seed)
+        if vocab_size is not None:
+            if word2vec_embedding is None:
+                word2vec_embedding = glorot_uniform_np((vocab_size, word_emb_dim), seed)  # nrms.py:40-43
+            self.word2vec_embedding = word2vec_embedding
+        self._get_loss(hparams.loss)
+        self._get_opt(hparams.optimizer, hparams.learning_rate)
+
+    def _get_loss(self, loss: str):
+        if loss == "cross_entropy_loss":
+            return "categorical_crossentropy"
+        if loss == "log_loss":
+            return "binary_crossentropy"
+        raise ValueError(f"this loss not defined {loss}")
+
+    def _get_opt(self, optimizer: str, lr: float):
+        if optimizer == "adam":
+            return "adam"
+        raise ValueError(f"this optimizer not defined {optimizer}")
+
+    def _set_loss(self, loss: str):
+        self._get_loss(loss)
+        self._engine.loss = loss
+
+    def _build_graph(self):
+        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
+
+    def recommend(self, loader, candidate_ids=None, **kwargs):
+        """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
+        return recommend(self, loader, candidate_ids, **kwargs)
 
 
 class EncoderModel:

@@ -15,30 +15,18 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._engine import glorot_uniform_np
 from ._engine_lstur import LSTUREngine
-from ._recommend import recommend
-from ._keras_like import ScorerModel, TrainModel
+from ._keras_like import ModelBase
 
 
-class LSTURModel:
+class LSTURModel(ModelBase):
     """LSTUR (An et al., ACL 2019): CNN title encoder with masked additive attention, and a GRU over the clicked titles
     combined with a trainable long-term user-id embedding -- as the GRU's initial state (type "ini") or concatenated with its
     output (type "con") (reference lstur.py)."""
 
     def __init__(self, hparams, word2vec_embedding: np.ndarray = None, word_emb_dim: int = 300, vocab_size: int = 32000,
                  seed: int = None, *, train_embedding: bool = True, device=None, process_group=None, bce_on: str = "logits"):
-        self.hparams = hparams
-        self.seed = seed
-        if seed is not None:
-            np.random.seed(seed)
-            torch.manual_seed(seed)
-        if word2vec_embedding is None:
-            self.word2vec_embedding = glorot_uniform_np((vocab_size, word_emb_dim), seed)
-        else:
-            self.word2vec_embedding = word2vec_embedding
-        self._get_loss(hparams.loss)
-        self._get_opt(hparams.optimizer, hparams.learning_rate)
+        self._preface(hparams, seed, word2vec_embedding, word_emb_dim, vocab_size)
         if getattr(hparams, "cnn_activation", "relu") != "relu":
             raise ValueError(f"cnn_activation {hparams.cnn_activation!r}: the HIP Conv1D implements relu")
         self._engine = LSTUREngine(
@@ -47,25 +35,6 @@ class LSTURModel:
             hparams.learning_rate, hparams.loss, seed=seed, train_embedding=train_embedding, device=device,
             process_group=process_group, bce_on=bce_on)
         self.model, self.scorer = self._build_graph()
-
-    def _get_loss(self, loss: str):
-        if loss == "cross_entropy_loss":
-            return "categorical_crossentropy"
-        if loss == "log_loss":
-            return "binary_crossentropy"
-        raise ValueError(f"this loss not defined {loss}")
-
-    def _get_opt(self, optimizer: str, lr: float):
-        if optimizer == "adam":
-            return "adam"
-        raise ValueError(f"this optimizer not defined {optimizer}")
-
-    def _set_loss(self, loss: str):
-        self._get_loss(loss)
-        self._engine.loss = loss
-
-    def _build_graph(self):
-        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
 
     # -- scorer bodies (lstur.py:191-200: sigmoid(news(pred_one) . user)) ------------------------------------------------------
     def _score_pairs(self, user, his, pred_one) -> torch.Tensor:
@@ -109,10 +78,6 @@ class LSTURModel:
     def _user_vectors_cached(self, cache, loader, i):
         user, his_idx = loader.user_index_eval_batch(i)[:2]
         return self._engine.user_vectors_cached(cache, user, his_idx), his_idx
-
-    def recommend(self, loader, candidate_ids=None, **kwargs):
-        """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
-        return recommend(self, loader, candidate_ids, **kwargs)
 
     def train_step(self, user, his, pred, y):
         """One optimizer step on raw arrays; returns the batch loss (device tensor)."""

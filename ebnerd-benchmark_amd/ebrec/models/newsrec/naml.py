@@ -17,13 +17,11 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._engine import glorot_uniform_np
 from ._engine_naml import NAMLEngine
-from ._recommend import recommend
-from ._keras_like import ScorerModel, TrainModel
+from ._keras_like import ModelBase
 
 
-class NAMLModel:
+class NAMLModel(ModelBase):
     """NAML (Wu et al., IJCAI 2019): attentive multi-view news encoder -- CNN + additive attention over the title and over the
     body, Dense views of the category and subcategory, additive attention over the four views -- and additive attention over
     the clicked news as the user encoder (reference naml.py)."""
@@ -31,18 +29,8 @@ class NAMLModel:
     def __init__(self, hparams, word2vec_embedding: np.ndarray = None, word_emb_dim: int = 300, vocab_size: int = 32000,
                  seed: int = None, *, n_users: int = 50000, train_embedding: bool = True, device=None, process_group=None,
                  bce_on: str = "logits"):
-        self.hparams = hparams
+        self._preface(hparams, seed, word2vec_embedding, word_emb_dim, vocab_size)
         self.n_users = n_users  # accepted and unused, as in the reference
-        self.seed = seed
-        if seed is not None:
-            np.random.seed(seed)
-            torch.manual_seed(seed)
-        if word2vec_embedding is None:
-            self.word2vec_embedding = glorot_uniform_np((vocab_size, word_emb_dim), seed)
-        else:
-            self.word2vec_embedding = word2vec_embedding
-        self._get_loss(hparams.loss)
-        self._get_opt(hparams.optimizer, hparams.learning_rate)
         for attr in ("cnn_activation", "dense_activation"):
             if getattr(hparams, attr, "relu") != "relu":
                 raise ValueError(f"{attr} {getattr(hparams, attr)!r}: the HIP Conv1D and categorical Dense implement relu")
@@ -52,25 +40,6 @@ class NAMLModel:
             hparams.subvert_emb_dim, hparams.dropout, hparams.learning_rate, hparams.loss, seed=seed,
             train_embedding=train_embedding, device=device, process_group=process_group, bce_on=bce_on)
         self.model, self.scorer = self._build_graph()
-
-    def _get_loss(self, loss: str):
-        if loss == "cross_entropy_loss":
-            return "categorical_crossentropy"
-        if loss == "log_loss":
-            return "binary_crossentropy"
-        raise ValueError(f"this loss not defined {loss}")
-
-    def _get_opt(self, optimizer: str, lr: float):
-        if optimizer == "adam":
-            return "adam"
-        raise ValueError(f"this optimizer not defined {optimizer}")
-
-    def _set_loss(self, loss: str):
-        self._get_loss(loss)
-        self._engine.loss = loss
-
-    def _build_graph(self):
-        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
 
     # -- scorer bodies (naml.py: sigmoid(news(pred_one) . user)) -------------------------------------------------------------
     def _score_pairs(self, *xs) -> torch.Tensor:
@@ -119,11 +88,6 @@ class NAMLModel:
         none = np.zeros(0, np.int32)
         _scores, user = self._engine.score_cached(cache, his_idx, none, none, sigmoid=True, return_user=True)
         return user, his_idx
-
-    def recommend(self, loader, candidate_ids=None, **kwargs):
-        """Each impression's top_n of one shared candidate list (``_recommend.recommend``): the candidates are articles of the
-        loader's catalogue, i.e. of its histories and in-view lists."""
-        return recommend(self, loader, candidate_ids, **kwargs)
 
     def train_step(self, *xs):
         """One optimizer step on raw arrays (the 8 inputs and y); returns the batch loss (device tensor)."""

@@ -22,29 +22,18 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._engine import glorot_uniform_np
 from ._engine_npa import NPAEngine
-from ._keras_like import ScorerModel, TrainModel
+from ._keras_like import ModelBase
 from ._recommend import npa_topk, recommend
 
 
-class NPAModel:
+class NPAModel(ModelBase):
     """NPA (Wu et al., KDD 2019): CNN title encoder and personalized attentive pooling at the word and news levels, both
     queried by a trainable user-id embedding (reference npa.py)."""
 
     def __init__(self, hparams, word2vec_embedding: np.ndarray = None, word_emb_dim: int = 300, vocab_size: int = 32000,
                  seed: int = None, *, train_embedding: bool = True, device=None, process_group=None, bce_on: str = "logits"):
-        self.hparams = hparams
-        self.seed = seed
-        if seed is not None:
-            np.random.seed(seed)
-            torch.manual_seed(seed)
-        if word2vec_embedding is None:
-            self.word2vec_embedding = glorot_uniform_np((vocab_size, word_emb_dim), seed)
-        else:
-            self.word2vec_embedding = word2vec_embedding
-        self._get_loss(hparams.loss)
-        self._get_opt(hparams.optimizer, hparams.learning_rate)
+        self._preface(hparams, seed, word2vec_embedding, word_emb_dim, vocab_size)
         if getattr(hparams, "cnn_activation", "relu") != "relu":
             raise ValueError(f"cnn_activation {hparams.cnn_activation!r}: the HIP Conv1D implements relu")
         self._engine = NPAEngine(
@@ -52,25 +41,6 @@ class NPAModel:
             hparams.window_size, hparams.attention_hidden_dim, hparams.user_emb_dim, hparams.dropout, hparams.learning_rate,
             hparams.loss, seed=seed, train_embedding=train_embedding, device=device, process_group=process_group, bce_on=bce_on)
         self.model, self.scorer = self._build_graph()
-
-    def _get_loss(self, loss: str):
-        if loss == "cross_entropy_loss":
-            return "categorical_crossentropy"
-        if loss == "log_loss":
-            return "binary_crossentropy"
-        raise ValueError(f"this loss not defined {loss}")
-
-    def _get_opt(self, optimizer: str, lr: float):
-        if optimizer == "adam":
-            return "adam"
-        raise ValueError(f"this optimizer not defined {optimizer}")
-
-    def _set_loss(self, loss: str):
-        self._get_loss(loss)
-        self._engine.loss = loss
-
-    def _build_graph(self):
-        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
 
     # -- scorer bodies (npa.py:188-199: sigmoid(news(pred_one) . user)) ------------------------------------------------------
     def _score_pairs(self, user, his, pred_one) -> torch.Tensor:

@@ -24,15 +24,14 @@ import torch
 
 from ebrec import _hip
 
-from ._engine import NRMSEngine, glorot_uniform_np
-from ._recommend import recommend
-from ._keras_like import EncoderModel, ScorerModel, TrainModel, dedup_rows
+from ._engine import NRMSEngine
+from ._keras_like import EncoderModel, ModelBase, dedup_rows
 
 WEIGHT_NAMES = ["news.emb", "news.attn.WQ", "news.attn.WK", "news.attn.WV", "news.att.W", "news.att.b", "news.att.q",
                 "user.attn.WQ", "user.attn.WK", "user.attn.WV", "user.att.W", "user.att.b", "user.att.q"]
 
 
-class NRMSModel:
+class NRMSModel(ModelBase):
     """NRMS (Wu et al., EMNLP-IJCNLP 2019) with the reference's quirks kept: P^T.V attention
     (layers.py:249), no masks, un-stabilised +1e-7 additive attention (layers.py:71-77)."""
 
@@ -41,19 +40,7 @@ class NRMSModel:
                  process_group=None, shard_table: bool = False, shard_mode: str = "alltoall",
                  deterministic: bool = True, shard_partition: str | None = None, shard_capacity_factor: float = 1.25,
                  table_grad_exchange: str = "auto", bce_on: str = "logits", precision: str = "exact"):
-        self.hparams = hparams
-        self.seed = seed
-        if seed is not None:
-            np.random.seed(seed)  # nrms.py:36-37 seeds the global generators
-            torch.manual_seed(seed)
-        if word2vec_embedding is None:
-            # Xavier initialisation of a (vocab_size, word_emb_dim) table (nrms.py:40-43)
-            self.word2vec_embedding = glorot_uniform_np((vocab_size, word_emb_dim), seed)
-        else:
-            self.word2vec_embedding = word2vec_embedding
-        # validate before touching the device (same errors as nrms.py:56-80)
-        self._get_loss(hparams.loss)
-        self._get_opt(hparams.optimizer, hparams.learning_rate)
+        self._preface(hparams, seed, word2vec_embedding, word_emb_dim, vocab_size)
         self._engine = NRMSEngine(
             np.asarray(self.word2vec_embedding), hparams.title_size, hparams.history_size, hparams.head_num,
             hparams.head_dim, hparams.attention_hidden_dim, hparams.dropout, hparams.learning_rate, hparams.loss,
@@ -66,26 +53,10 @@ class NRMSModel:
         self.model, self.scorer = self._build_graph()
 
     # -- same helper names as the reference ------------------------------------------
-    def _get_loss(self, loss: str):
-        if loss == "cross_entropy_loss":
-            return "categorical_crossentropy"
-        if loss == "log_loss":
-            return "binary_crossentropy"
-        raise ValueError(f"this loss not defined {loss}")
-
-    def _get_opt(self, optimizer: str, lr: float):
-        if optimizer == "adam":
-            return "adam"
-        raise ValueError(f"this optimizer not defined {optimizer}")
-
-    def _set_loss(self, loss: str):
-        self._get_loss(loss)
-        self._engine.loss = loss
-
     def _build_graph(self):
         self.newsencoder = EncoderModel(self._encode_news, "news_encoder")
         self.userencoder = EncoderModel(self._encode_users, "user_encoder")
-        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
+        return super()._build_graph()
 
     # -- sub-model bodies --------------------------------------------------------------
     def _encode_news(self, ids):
@@ -157,10 +128,6 @@ class NRMSModel:
     def _user_vectors_cached(self, cache, loader, i):
         his_idx = loader.index_eval_batch(i)[0]
         return self._users_indexed(cache, his_idx), his_idx
-
-    def recommend(self, loader, candidate_ids=None, **kwargs):
-        """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
-        return recommend(self, loader, candidate_ids, **kwargs)
 
     # -- interchange ------------------------------------------------------------------
     def from_keras_weight_list(self, weights):

@@ -18,46 +18,23 @@ import torch
 from ebrec import _hip
 
 from ._engine_docvec import DocVecEngine
-from ._recommend import recommend
-from ._keras_like import EncoderModel, ScorerModel, TrainModel, dedup_rows
+from ._keras_like import EncoderModel, ModelBase, dedup_rows
 
 
-class NRMSDocVec:
+class NRMSDocVec(ModelBase):
     def __init__(self, hparams, seed: int = None, *, device=None, process_group=None, bce_on: str = "logits"):
-        self.hparams = hparams
-        self.seed = seed
-        if seed is not None:
-            np.random.seed(seed)  # nrms_docvec.py:31-32
-            torch.manual_seed(seed)
-        self._get_loss(hparams.loss)
-        self._get_opt(hparams.optimizer, hparams.learning_rate)
+        self._preface(hparams, seed)
         self._engine = DocVecEngine(
             hparams.title_size, hparams.newsencoder_units_per_layer, hparams.history_size, hparams.head_num,
             hparams.head_dim, hparams.attention_hidden_dim, hparams.dropout, hparams.learning_rate, hparams.loss,
             hparams.newsencoder_l2_regularization, seed=seed, device=device, process_group=process_group, bce_on=bce_on)
         self.model, self.scorer = self._build_graph()
 
-    def _get_loss(self, loss: str):
-        if loss == "cross_entropy_loss":
-            return "categorical_crossentropy"
-        if loss == "log_loss":
-            return "binary_crossentropy"
-        raise ValueError(f"this loss not defined {loss}")
-
-    def _get_opt(self, optimizer: str, lr: float):
-        if optimizer == "adam":
-            return "adam"
-        raise ValueError(f"this optimizer not defined {optimizer}")
-
-    def _set_loss(self, loss: str):
-        self._get_loss(loss)
-        self._engine.loss = loss
-
     def _build_graph(self):
         self.newsencoder = EncoderModel(lambda x: self._engine.encode_news(np.asarray(x, dtype=np.float32).reshape(-1, self._engine.Din)),
                                         "news_encoder")
         self.userencoder = EncoderModel(lambda x: self._engine.encode_users(np.asarray(x, dtype=np.float32)), "user_encoder")
-        return TrainModel(self, self._engine.weight_names()), ScorerModel(self)
+        return super()._build_graph()
 
     def _score_pairs(self, his: np.ndarray, pred_one: np.ndarray) -> torch.Tensor:
         eng = self._engine
@@ -111,10 +88,6 @@ class NRMSDocVec:
     def _user_vectors_cached(self, cache, loader, i):
         his_idx = loader.index_eval_batch(i)[0]
         return self._users_indexed(cache, his_idx), his_idx
-
-    def recommend(self, loader, candidate_ids=None, **kwargs):
-        """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
-        return recommend(self, loader, candidate_ids, **kwargs)
 
     def train_step(self, his, pred, y):
         return self._engine.train_step(his, pred, y)

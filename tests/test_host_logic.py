@@ -155,3 +155,49 @@ def test_bce_default_is_the_one_the_tf_golden_tests_expect():
     assert [loss_kind_of("cross_entropy_loss", "probs"), loss_kind_of("log_loss", "logits"), loss_kind_of("log_loss", "probs")] == [0, 1, 2]
     with pytest.raises(ValueError):
         loss_kind_of("log_loss", "sigmoid")
+
+
+_ROW = (IndexError, "article row out of range for the encoded catalogue")
+_USER = (IndexError, "user index out of range [0, 7] for the user embedding table")
+_TOKEN = (IndexError, "token id out of range [0, 50) for the embedding table")
+_CAT = (IndexError, "category id out of range: vert ids must lie in [0, 3), subvert ids in [0, 5)")
+_RANGE = (FloatingPointError, "embedding gradient left the range of the deterministic fixed-point accumulator: the run has diverged")
+# flag attribute -> what it raises, in the engine's raise priority (first = raised when several are set)
+_USER_TABLE_FLAGS = {"row_oob_flag": _ROW, "user_oob_flag": _USER, "oob_flag": _TOKEN, "range_flag": _RANGE}
+_NAML_FLAGS = {"row_oob_flag": _ROW, "oob_flag": _TOKEN, "cat_oob_flag": _CAT, "range_flag": _RANGE}
+
+
+def _flag_engine(module, cls_name):
+    """The engine as bare object with CPU flag tensors and the attributes its messages read: _check_oob needs no device."""
+    import importlib
+
+    import torch
+
+    cls = getattr(importlib.import_module(f"ebrec.models.newsrec.{module}"), cls_name)
+    eng = object.__new__(cls)
+    eng.V, eng.n_users, eng.n_vert, eng.n_sub = 50, 7, 3, 5
+    flags = _NAML_FLAGS if cls_name == "NAMLEngine" else _USER_TABLE_FLAGS
+    for attr in flags:
+        setattr(eng, attr, torch.zeros(1, dtype=torch.int32))
+    return eng, flags
+
+
+@pytest.mark.parametrize("module,cls_name", [("_engine_lstur", "LSTUREngine"), ("_engine_npa", "NPAEngine"), ("_engine_naml", "NAMLEngine")])
+def test_check_oob_raises_the_first_set_flag_in_priority_order_and_clears_all(module, cls_name):
+    import itertools
+    import re
+
+    eng, flags = _flag_engine(module, cls_name)
+    order = list(flags)
+    eng._check_oob()  # nothing set: nothing raised
+    eng.check_oob()
+    for k in range(1, len(order) + 1):
+        for combo in itertools.combinations(order, k):
+            for attr in combo:
+                getattr(eng, attr).fill_(3 if attr == "range_flag" else 1)  # any non-zero value counts
+            exc, msg = flags[min(combo, key=order.index)]
+            with pytest.raises(exc, match="^" + re.escape(msg) + "$") as err:
+                eng._check_oob()
+            assert type(err.value) is exc, combo
+            assert all(int(getattr(eng, attr)) == 0 for attr in order), combo  # every flag is cleared, not only the raised one
+            eng._check_oob()  # so the next read is clean
