@@ -5,3 +5,4 @@ from .beyond_accuracy import Calibration, Coverage, Distribution, IntralistDiver
 from .device_metrics import DeviceMetricEvaluator, RaggedLists  # noqa: F401
 from .rerank import MMR, Calibrated, calibrated_rerank, history_distribution, mmr_rerank  # noqa: F401
 from .freshness import Freshness  # noqa: F401
+from .catalogue_ranks import rank_metrics  # noqa: F401

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from ._engine import eval_loss_from_news, glorot_uniform_np
-from ._recommend import recommend
+from ._recommend import rank_targets, recommend
 from .callbacks import Callback, History, StreamingAUC
 
 
@@ -434,6 +434,10 @@ class ModelBase:
     def recommend(self, loader, candidate_ids=None, **kwargs):
         """Each impression's top_n of one shared candidate list (``_recommend.recommend``)."""
         return recommend(self, loader, candidate_ids, **kwargs)
+
+    def rank_targets(self, loader, targets=None, candidate_ids=None, **kwargs):
+        """Where each impression's clicked article stands among all candidates (``_recommend.rank_targets``)."""
+        return rank_targets(self, loader, targets, candidate_ids, **kwargs)
 
 
 class EncoderModel:

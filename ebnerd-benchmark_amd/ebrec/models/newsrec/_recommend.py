@@ -34,8 +34,16 @@ lam * score - (1 - lam) * KL(target || the list's label distribution).
 published inside its own time window: the candidates are sorted by publish time, which makes an impression's admissible set one
 range [lo, hi) of positions, the users of a launch are sorted by ``lo``, and ``ebn_topk_score_window_f32`` lets a 128-user
 workgroup walk only the candidate tiles its users' ranges meet (``topk_window`` below).
+
+``rank_targets(model, loader, targets=None, candidate_ids=None, ...)`` is the accuracy side of the same lists: where the article an
+impression clicked stands among ALL candidates, under the same exclusion and freshness rules.  It shares this module's host path
+with ``recommend`` (checks, candidate rows, windows, cache, batching, the sort by ``lo``, the flags) and launches
+``ebn_target_rank_f32`` (``target_rank`` below): the same GEMM with a count in place of the selection, 12 bytes per pair.
+``ebrec.evaluation.rank_metrics`` turns the ranks into hit-rate@k, MRR and nDCG@k.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -200,6 +208,118 @@ def npa_topk(users: torch.Tensor, Q: torch.Tensor, Ua_all: torch.Tensor, Vd_all:
     return pos, score
 
 
+def target_rank(users: torch.Tensor, news_all: torch.Tensor, cand_rows, target_pos: torch.Tensor, window, exclude, sigmoid: bool,
+                flags: torch.Tensor, n_splits: int = 0):
+    """One ebn_target_rank_f32 call on device tensors: target_pos [U] int32 positions in the candidate list (< 0: none), window
+    [U, 2] int32 or None -> (rank [U] int32: 1-based place of the target in ``topk``'s order, 0 = not ranked; count [U] int32:
+    the user's admissible candidates; score [U] float32: the target's score, -inf where rank is 0); ``flags`` accumulates."""
+    U, F = users.shape
+    n_rows = news_all.shape[0]
+    M = n_rows if cand_rows is None else cand_rows.shape[0]
+    X = 0 if exclude is None else exclude.shape[1]
+    if target_pos.shape != (U,) or target_pos.dtype != torch.int32 or not target_pos.is_contiguous():
+        raise ValueError(f"target_pos must be a contiguous [{U}] int32 tensor, got {tuple(target_pos.shape)} {target_pos.dtype}")
+    if window is not None and (window.shape != (U, 2) or window.dtype != torch.int32 or not window.is_contiguous()):
+        raise ValueError(f"window must be a contiguous [{U}, 2] int32 tensor, got {tuple(window.shape)} {window.dtype}")
+    rank = torch.empty(U, dtype=torch.int32, device=users.device)
+    count = torch.empty(U, dtype=torch.int32, device=users.device)
+    score = torch.empty(U, dtype=torch.float32, device=users.device)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_topk_auto_splits(U, M))
+    ws_bytes = int(lib.ebn_target_rank_workspace_bytes(U, max(splits, 1)))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=users.device)
+    _hip.call("ebn_target_rank_f32", _hip.ptr(users), _hip.ptr(news_all), n_rows, _hip.ptr(cand_rows), M, _hip.ptr(target_pos),
+              _hip.ptr(window), _hip.ptr(exclude), X, 1 if sigmoid else 0, splits, _hip.ptr(rank), _hip.ptr(count), _hip.ptr(score),
+              _hip.ptr(flags), _hip.ptr(ws), ws.numel(), U, F, _hip.stream_handle())
+    return rank, count, score
+
+
+def _check_window(model, window):
+    if window is not None:
+        if getattr(model, "_recommend_topk", None) is not None:
+            raise NotImplementedError(f"window= is not supported for {type(model).__name__}: its scoring launch has no windowed form")
+        if not isinstance(window, Freshness):
+            raise ValueError(f"window must be None or a Freshness(published, max_age, min_age), got {type(window).__name__}")
+
+
+def _by_publish_time(window, loader, cand_ids, rows):
+    """the candidates by publish time -- positions, lookup rows and the final id mapping alike -- and the impressions' ranges
+    [n_impressions, 2] int32 in loader order"""
+    order, win_lo, win_hi = window.windows(cand_ids, window.impression_times(loader))
+    return cand_ids[order], rows[order], np.ascontiguousarray(np.stack([win_lo, win_hi], 1), dtype=np.int32)
+
+
+def _launch_batches(model, cache, loader, device, need_his, exclude_history, win_all, users_per_call, run, check_history=None,
+                    repeat=None):
+    """The loop both ``recommend`` and ``rank_targets`` run over the loader's batches: user vectors (and history rows, and windows)
+    are collected until ``users_per_call`` impressions are pending, then launched together.  ``repeat(first, n)`` (or None) gives,
+    for the n impressions from loader row ``first`` on, a device index [P] of the impressions the launch's rows stand for (an
+    impression may be taken several times, or not at all).  With windows the rows of a launch are sorted by ``lo`` (stable), so
+    that neighbours share their candidate tiles.  ``run(users, his, window, first, perm)`` (``perm``: the sort, or None) -> a tuple
+    of tensors with one leading entry per row; they come back in the order the rows had before the sort.  -> the list of those
+    tuples, one per launch."""
+    outs, users, his, wins, pending, first = [], [], [], [], 0, 0
+
+    def flush():
+        nonlocal pending, first
+        if not users:
+            return
+        u = torch.cat(users).contiguous()
+        hh = torch.cat(his).contiguous() if need_his else None
+        wd = torch.from_numpy(np.concatenate(wins)).to(device) if win_all is not None else None
+        n = u.shape[0]
+        if repeat is not None:
+            idx = repeat(first, n)
+            u = u[idx].contiguous()
+            hh = hh[idx].contiguous() if need_his else None
+            wd = wd[idx].contiguous() if wd is not None else None
+        perm = None
+        if wd is not None:  # users, histories and windows sorted by lo (stable): neighbours share their candidate tiles
+            perm = torch.argsort(wd[:, 0], stable=True)
+            u, wd = u[perm].contiguous(), wd[perm].contiguous()
+            hh = hh[perm].contiguous() if need_his else None
+        out = run(u, hh, wd, first, perm)
+        if perm is not None:  # back to loader order
+            out = tuple(torch.empty_like(t).index_copy_(0, perm, t) for t in out)
+        outs.append(out)
+        users.clear()
+        his.clear()
+        wins.clear()
+        pending = 0
+        first += n
+
+    for i in range(len(loader)):
+        user, his_rows = model._user_vectors_cached(cache, loader, i)
+        if need_his:
+            h = torch.as_tensor(np.ascontiguousarray(his_rows, dtype=np.int32)).to(device)
+            if exclude_history and h.shape[1] > MAX_EXCLUDE:
+                raise ValueError(f"exclude_history supports histories of at most {MAX_EXCLUDE} articles, got {h.shape[1]}")
+            if check_history is not None:
+                check_history(h)
+            if his and his[0].shape[1] != h.shape[1]:
+                flush()
+            his.append(h)
+        if win_all is not None:
+            w = win_all[i * loader.batch_size: i * loader.batch_size + user.shape[0]]
+            if len(w) != user.shape[0]:
+                raise ValueError(f"batch {i} has {user.shape[0]} impressions, the loader's frame holds {len(w)} rows for it")
+            wins.append(w)
+        users.append(user)
+        pending += user.shape[0]
+        if pending >= users_per_call:
+            flush()
+    flush()
+    return outs
+
+
+def _raise_flags(flags):
+    row_bad, nan_seen = (int(v) for v in flags.cpu().tolist())
+    if row_bad:
+        raise IndexError("candidate row out of range for the encoded catalogue")
+    if nan_seen:
+        raise FloatingPointError("NaN scores: the model's user or news vectors are not finite")
+
+
 def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True, return_scores=False, scores="sigmoid", fill_id=-1,
               users_per_call=65536, rerank=None, window=None):
     """ids [n_impressions, top_n] of the loader's article ids: each impression's ``top_n`` best of ``candidate_ids`` (``None``:
@@ -223,21 +343,16 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     window holding fewer than ``top_n`` candidates gives a list padded with ``fill_id``; ``rerank=`` works on top unchanged (its
     pool is the window's best, a history target is not touched by the window).  Not for models with a scoring launch of their
     own (NPA)."""
-    if window is not None:
-        if getattr(model, "_recommend_topk", None) is not None:
-            raise NotImplementedError(f"window= is not supported for {type(model).__name__}: its scoring launch has no windowed form")
-        if not isinstance(window, Freshness):
-            raise ValueError(f"window must be None or a Freshness(published, max_age, min_age), got {type(window).__name__}")
+    _check_window(model, window)
     _check(model, loader, top_n, scores)
     top_n = int(top_n)
     index = model._recommend_index(loader)
     cand_ids, rows = candidate_rows(index, candidate_ids)
     if top_n > len(rows):
         raise ValueError(f"top_n = {top_n} is larger than the number of candidates ({len(rows)})")
-    if window is not None:  # the candidates by publish time from here on: positions, lookup rows and the final id mapping alike
-        order, win_lo, win_hi = window.windows(cand_ids, window.impression_times(loader))
-        cand_ids, rows = cand_ids[order], rows[order]
-        win_all = np.ascontiguousarray(np.stack([win_lo, win_hi], 1), dtype=np.int32)  # [n_impressions, 2], loader order
+    win_all = None
+    if window is not None:  # the candidates by publish time from here on
+        cand_ids, rows, win_all = _by_publish_time(window, loader, cand_ids, rows)
     if rerank is not None:
         pool, lookup_rows = _check_rerank(rerank, top_n, cand_ids)
     cache, news_all = model._recommend_cache(loader)
@@ -264,83 +379,127 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
         launch = lambda u, ex, k, w: topk(u, news_all, cand_d, ex, k, sigmoid, flags)
     else:
         launch = lambda u, ex, k, w: model_topk(cache, u, cand_d, ex, k, sigmoid, flags)
-    pos_out, score_out, users, his, wins, pending = [], [], [], [], [], 0
 
-    def flush():
-        nonlocal pending
-        if not users:
-            return
-        u = torch.cat(users).contiguous()
-        hh = torch.cat(his).contiguous() if need_his else None
-        wd = perm = None
-        if window is not None:  # users, histories and windows sorted by lo (stable): neighbours share their candidate tiles
-            wd = torch.from_numpy(np.concatenate(wins)).to(device)
-            perm = torch.argsort(wd[:, 0], stable=True)
-            u, wd = u[perm].contiguous(), wd[perm].contiguous()
-            hh = hh[perm].contiguous() if need_his else None
+    def run(u, hh, wd, first, perm):
         ex = hh if exclude_history else None
         if rerank is None:
-            p, s = launch(u, ex, top_n, wd)
-        else:  # the pool, its rows in the lookup's table (-1 stays -1), the greedy picks, and the picks' positions and scores
-            pp, ps = launch(u, ex, pool, wd)
-            pool_rows = torch.where(pp >= 0, row_of_pos[pp.clamp(min=0).long()], pp).contiguous()
-            if not calibrated:
-                sel, _ = mmr_select(unit, pool_rows, ps, top_n, rerank.lam, flags)
+            return launch(u, ex, top_n, wd)
+        # the pool, its rows in the lookup's table (-1 stays -1), the greedy picks, and the picks' positions and scores
+        pp, ps = launch(u, ex, pool, wd)
+        pool_rows = torch.where(pp >= 0, row_of_pos[pp.clamp(min=0).long()], pp).contiguous()
+        if not calibrated:
+            sel, _ = mmr_select(unit, pool_rows, ps, top_n, rerank.lam, flags)
+        else:
+            if from_history:  # history rows of the catalogue -> rows of the label table (outside the catalogue: the padding)
+                inside = (hh >= 0) & (hh < lookup_row_of_news.shape[0])
+                hist_rows = torch.where(inside, lookup_row_of_news[hh.clamp(0, lookup_row_of_news.shape[0] - 1).long()],
+                                        torch.full_like(hh, -1)).contiguous()
+                w = None if slot_w is None else torch.from_numpy(slot_w.astype(np.float32)).to(device)
+                target = label_target(unit, hist_rows, w, flags)
             else:
-                if from_history:  # history rows of the catalogue -> rows of the label table (outside the catalogue: the padding)
-                    inside = (hh >= 0) & (hh < lookup_row_of_news.shape[0])
-                    hist_rows = torch.where(inside, lookup_row_of_news[hh.clamp(0, lookup_row_of_news.shape[0] - 1).long()],
-                                            torch.full_like(hh, -1)).contiguous()
-                    w = None if slot_w is None else torch.from_numpy(slot_w.astype(np.float32)).to(device)
-                    target = label_target(unit, hist_rows, w, flags)
-                else:
-                    target = shared
-                sel, _ = calibrated_select(unit, pool_rows, ps, target, top_n, rerank.lam, rerank.alpha, flags)
-            kept = sel.clamp(min=0).long()
-            p = torch.where(sel >= 0, pp.gather(1, kept), sel)
-            s = torch.where(sel >= 0, ps.gather(1, kept), torch.full_like(ps[:, :1], float("-inf")))
-        if perm is not None:  # back to loader order
-            p, s = torch.empty_like(p).index_copy_(0, perm, p), torch.empty_like(s).index_copy_(0, perm, s)
-        pos_out.append(p)
-        score_out.append(s)
-        users.clear()
-        his.clear()
-        wins.clear()
-        pending = 0
+                target = shared
+            sel, _ = calibrated_select(unit, pool_rows, ps, target, top_n, rerank.lam, rerank.alpha, flags)
+        kept = sel.clamp(min=0).long()
+        p = torch.where(sel >= 0, pp.gather(1, kept), sel)
+        s = torch.where(sel >= 0, ps.gather(1, kept), torch.full_like(ps[:, :1], float("-inf")))
+        return p, s
 
-    for i in range(len(loader)):
-        user, his_rows = model._user_vectors_cached(cache, loader, i)
-        if need_his:
-            h = torch.as_tensor(np.ascontiguousarray(his_rows, dtype=np.int32)).to(device)
-            if exclude_history and h.shape[1] > MAX_EXCLUDE:
-                raise ValueError(f"exclude_history supports histories of at most {MAX_EXCLUDE} articles, got {h.shape[1]}")
-            if from_history and not 1 <= h.shape[1] <= MAX_HISTORY:
-                raise ValueError(f"a history target supports histories of 1 to {MAX_HISTORY} articles, got {h.shape[1]}")
-            if from_history and slot_w is not None and len(slot_w) != h.shape[1]:
-                raise ValueError(f"history_weights has {len(slot_w)} entries, the loader's histories {h.shape[1]} slots")
-            if his and his[0].shape[1] != h.shape[1]:
-                flush()
-            his.append(h)
-        if window is not None:
-            w = win_all[i * loader.batch_size: i * loader.batch_size + user.shape[0]]
-            if len(w) != user.shape[0]:
-                raise ValueError(f"batch {i} has {user.shape[0]} impressions, the loader's frame holds {len(w)} rows for it")
-            wins.append(w)
-        users.append(user)
-        pending += user.shape[0]
-        if pending >= users_per_call:
-            flush()
-    flush()
+    def check_history(h):
+        if from_history and not 1 <= h.shape[1] <= MAX_HISTORY:
+            raise ValueError(f"a history target supports histories of 1 to {MAX_HISTORY} articles, got {h.shape[1]}")
+        if from_history and slot_w is not None and len(slot_w) != h.shape[1]:
+            raise ValueError(f"history_weights has {len(slot_w)} entries, the loader's histories {h.shape[1]} slots")
+
+    outs = _launch_batches(model, cache, loader, device, need_his, exclude_history, win_all, users_per_call, run, check_history)
+    pos_out, score_out = [o[0] for o in outs], [o[1] for o in outs]
     if not pos_out:
         ids = np.full((0, top_n), fill_id, dtype=np.asarray(cand_ids).dtype if len(cand_ids) else np.int64)
         return (ids, np.zeros((0, top_n), np.float32)) if return_scores else ids
     pos = torch.cat(pos_out).cpu().numpy().astype(np.int64)
-    row_bad, nan_seen = (int(v) for v in flags.cpu().tolist())
-    if row_bad:
-        raise IndexError("candidate row out of range for the encoded catalogue")
-    if nan_seen:
-        raise FloatingPointError("NaN scores: the model's user or news vectors are not finite")
+    _raise_flags(flags)
     ids = np.where(pos >= 0, cand_ids[np.maximum(pos, 0)], np.asarray(fill_id, dtype=cand_ids.dtype))
     if return_scores:
         return ids, torch.cat(score_out).cpu().numpy()
     return ids
+
+
+@dataclass
+class TargetRanks:
+    """One entry per (impression, target) pair, in loader order: ``impression`` the row of ``loader.X``, ``target_id`` the
+    article, ``rank`` its 1-based place among the impression's admissible candidates in ``recommend``'s order (0: not ranked --
+    no candidate, outside the window, excluded), ``count`` the number of those candidates, ``score`` its score (-inf where
+    ``rank`` is 0).  ``ebrec.evaluation.rank_metrics(ranks.rank, counts=ranks.count)`` gives the metrics."""
+    impression: np.ndarray
+    target_id: np.ndarray
+    rank: np.ndarray
+    count: np.ndarray
+    score: np.ndarray
+
+    def __len__(self):
+        return len(self.rank)
+
+
+def _target_pairs(loader, targets):
+    """(impression [P] int64, target id [P]) in loader order.  ``None``: every in-view article labelled 1 in ``loader.y``."""
+    n = len(loader.X)
+    if targets is None:
+        inview = loader.X[loader.inview_col].tolist() if n else []
+        per_row = [[a for a, l in zip(ids, labels) if l == 1] for ids, labels in zip(inview, loader.y)]
+    else:
+        per_row = [np.asarray(t).reshape(-1).tolist() for t in targets]
+        if len(per_row) != n:
+            raise ValueError(f"targets must hold one id or one list of ids per impression: the loader has {n} rows, got {len(per_row)}")
+    imp = np.repeat(np.arange(n, dtype=np.int64), [len(t) for t in per_row])
+    flat = [a for t in per_row for a in t]
+    return imp, (np.asarray(flat) if flat else np.zeros(0, np.int64))
+
+
+def rank_targets(model, loader, targets=None, candidate_ids=None, exclude_history=True, window=None, scores="sigmoid",
+                 users_per_call=65536) -> TargetRanks:
+    """Where each impression's target article stands among ALL of ``candidate_ids`` (``None``: every article of the loader's
+    index) by the model's score: the unsampled counterpart of the in-view metrics, under ``recommend``'s rules.  ``rank`` r <= k
+    holds exactly when ``recommend(loader, candidate_ids, top_n=k, ...)`` with the same ``exclude_history`` and ``window`` has the
+    target at index r - 1, and ``score`` is that slot's score.
+    ``targets=None``: every in-view article labelled 1 in ``loader.y`` -- an impression with two clicks gives two pairs; else one
+    id or a list of ids per impression.  A target that is not in the candidate list (or not in the loader's article index) is
+    no error: its pair comes back with rank 0, as does a target the impression's history excludes or its window does not hold.
+    A target id that occurs twice in ``candidate_ids`` is its first occurrence (under ``window=``: the first after the sort by
+    publish time).  Not for models with a scoring launch of their own (NPA)."""
+    if getattr(model, "_recommend_topk", None) is not None:
+        raise NotImplementedError(f"rank_targets is not supported for {type(model).__name__}: its scoring launch has no counting form")
+    _check_window(model, window)
+    _check(model, loader, 1, scores)
+    index = model._recommend_index(loader)
+    cand_ids, rows = candidate_rows(index, candidate_ids)
+    win_all = None
+    if window is not None:  # the candidates by publish time from here on: a target's position is its position after the sort
+        cand_ids, rows, win_all = _by_publish_time(window, loader, cand_ids, rows)
+    imp, target_ids = _target_pairs(loader, targets)
+    first_pos = {}
+    for j, a in enumerate(cand_ids.tolist()):
+        first_pos.setdefault(a, j)
+    pos_all = np.fromiter((first_pos.get(a, -1) for a in target_ids.tolist()), dtype=np.int32, count=len(target_ids))
+    cache, news_all = model._recommend_cache(loader)
+    news_all = news_all.contiguous()
+    device = news_all.device
+    cand_d = torch.from_numpy(rows).to(device)
+    flags = torch.zeros(2, dtype=torch.int32, device=device)
+    sigmoid = scores == "sigmoid"
+    starts = np.searchsorted(imp, np.arange(len(loader.X) + 1))  # the pairs of impression r: starts[r] .. starts[r + 1]
+    target_of_launch = []
+
+    def repeat(first, n):
+        lo, hi = starts[first], starts[first + n]
+        target_of_launch.append(torch.from_numpy(pos_all[lo:hi]).to(device))
+        return torch.from_numpy(imp[lo:hi] - first).to(device)
+
+    def run(u, hh, wd, first, perm):
+        tp = target_of_launch.pop()
+        tp = (tp if perm is None else tp[perm]).contiguous()
+        return target_rank(u, news_all, cand_d, tp, wd, hh if exclude_history else None, sigmoid, flags)
+
+    outs = _launch_batches(model, cache, loader, device, exclude_history, exclude_history, win_all, users_per_call, run, repeat=repeat)
+    cat = lambda k, dtype: (torch.cat([o[k] for o in outs]).cpu().numpy() if outs else np.zeros(0, dtype))
+    rank, count, score = cat(0, np.int32), cat(1, np.int32), cat(2, np.float32)
+    _raise_flags(flags)
+    return TargetRanks(impression=imp, target_id=target_ids, rank=rank, count=count, score=score)

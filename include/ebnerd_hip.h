@@ -1021,6 +1021,38 @@ int ebn_topk_score_window_f32(const float* users, const float* news_all, int64_t
                               int32_t* out_pos, float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes,
                               int64_t U, int32_t F, ebn_stream_t stream);
 
+/* ---- full-catalogue rank of one target candidate per user (the accuracy side of the same workflow,
+ * examples/beyond_accuracy/make_beyond_accuracy.ipynb, cell "Your Model": where the clicked article stands among all candidates the
+ * top-N is drawn from -- hit-rate@k, MRR and nDCG@k over the candidate list; scorers as above: act(user . news)) ---------------------
+ * Everything not said here is ebn_topk_score_window_f32's contract: the operands and cand_rows == NULL, duplicate rows being distinct
+ * candidates, exclude [U, X] matching by catalogue row, the clamping of window [U, 2], the limits (F % 4 == 0, 4 <= F <= 8192,
+ * X <= 256: EBN_ERR_UNSUPPORTED; users / news_all 16-byte aligned: EBN_ERR_ALIGN), the argument codes (all checked on the host before
+ * anything is launched: a failing call writes nothing), U == 0 (nothing to do), n_splits (0 = ebn_topk_auto_splits; the ranges
+ * divide the tiles a workgroup's windows meet) and flags[0] / flags[1], including the either-value clause for a row outside the
+ * table that lies inside a workgroup's span but in nobody's window.  window == NULL: no windows, every position is inside.
+ * s(u, c) = users[u, :] . news_all[cand_rows[c], :] has the BITS ebn_topk_score_f32 gives the same (user row, catalogue row) pair:
+ * the same v_mfma_f32_32x32x2_f32 fma chain in the same k order.  Position c is admissible for user u when it lies in u's clamped
+ * window, cand_rows[c] lies in [0, n_rows) and is not in exclude[u, :], and s(u, c) is not NaN.  target_pos [U] int32 on the DEVICE
+ * (required, EBN_ERR_BAD_ARG): the position of the user's target in the candidate list; < 0: no target; >= M: no target and
+ * flags[0] is set.  With t = s(u, target_pos[u]):
+ *   out_count[u] = the number of admissible positions
+ *   out_rank[u]  = 1 + #{admissible c != target : s(u, c) > t or (s(u, c) == t and c < target_pos[u])} -- the target's index + 1 in
+ *                  the total order of ebn_topk_score_f32 (score descending, then position ascending; +-inf rank like numbers) --
+ *                  or 0 when there is no target or the target position is itself not admissible (a NaN t inside the window also
+ *                  sets flags[1], a target row outside the table inside the window flags[0])
+ *   out_score[u] = t (mode 0) or sigmoid(t) (mode 1) when out_rank[u] > 0, else -inf
+ * M == 0: rank 0, count 0, score -inf.  The three outputs depend neither on n_splits, nor on the run, nor on which other users
+ * share the launch.  More than one range of candidates: each writes its two partial counts per user to the workspace (16-byte
+ * aligned, at least ebn_target_rank_workspace_bytes(U, n_splits) bytes, else EBN_ERR_BAD_ARG) and a second launch adds them --
+ * integer sums, the order is free; no atomics on global memory.                                                                   */
+/* Bytes of workspace for n_splits >= 1 candidate ranges (a nominal 16 for one range, which needs none); 0 for sizes outside the
+ * limits, never negative.  Pure host query.                                                                                       */
+int64_t ebn_target_rank_workspace_bytes(int64_t n_users, int32_t n_splits);
+int ebn_target_rank_f32(const float* users, const float* news_all, int64_t n_rows, const int32_t* cand_rows, int64_t M,
+                        const int32_t* target_pos, const int32_t* window, const int32_t* exclude, int32_t X, int32_t mode,
+                        int32_t n_splits, int32_t* out_rank, int32_t* out_count, float* out_score, int32_t* flags, void* workspace,
+                        int64_t workspace_bytes, int64_t U, int32_t F, ebn_stream_t stream);
+
 /* ---- top-N recommendation for NPA from the once-encoded catalogue (the same workflow for npa.py: its news vector depends on the
  * user -- layers.py:312-339 PersonalizedAttentivePooling -- so there is no [n_rows, F] catalogue for ebn_topk_score_f32) ------------
  * Per user u and candidate row = cand_rows[c], from what NPAEngine.encode_catalogue keeps (Ua_all [n_rows, L, A] tanh'd attention
