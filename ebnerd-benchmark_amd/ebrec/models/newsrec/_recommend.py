@@ -39,7 +39,13 @@ workgroup walk only the candidate tiles its users' ranges meet (``topk_window`` 
 impression clicked stands among ALL candidates, under the same exclusion and freshness rules.  It shares this module's host path
 with ``recommend`` (checks, candidate rows, windows, cache, batching, the sort by ``lo``, the flags) and launches
 ``ebn_target_rank_f32`` (``target_rank`` below): the same GEMM with a count in place of the selection, 12 bytes per pair.
-``ebrec.evaluation.rank_metrics`` turns the ranks into hit-rate@k, MRR and nDCG@k.
+``ebrec.evaluation.rank_metrics`` turns the ranks into hit-rate@k, MRR and nDCG@k.  A model with a scoring launch of its own offers
+its counting form as a fifth hook, passed to the same body (``_rank_targets``):
+
+    _rank_launch(cache, users, cand_rows, target_pos, window, exclude, sigmoid, flags) -> (rank [U], count [U], score [U])
+
+NPA's is ``ebn_npa_target_rank_f32`` (``npa_target_rank`` below) behind ``NPAModel.rank_targets_pairwise``; it takes windows, while
+NPA's windowed top-N lists do not exist yet.
 """
 from __future__ import annotations
 
@@ -231,6 +237,32 @@ def target_rank(users: torch.Tensor, news_all: torch.Tensor, cand_rows, target_p
     _hip.call("ebn_target_rank_f32", _hip.ptr(users), _hip.ptr(news_all), n_rows, _hip.ptr(cand_rows), M, _hip.ptr(target_pos),
               _hip.ptr(window), _hip.ptr(exclude), X, 1 if sigmoid else 0, splits, _hip.ptr(rank), _hip.ptr(count), _hip.ptr(score),
               _hip.ptr(flags), _hip.ptr(ws), ws.numel(), U, F, _hip.stream_handle())
+    return rank, count, score
+
+
+def npa_target_rank(users: torch.Tensor, Q: torch.Tensor, Ua_all: torch.Tensor, Vd_all: torch.Tensor, cand_rows, target_pos: torch.Tensor,
+                    window, exclude, sigmoid: bool, flags: torch.Tensor, n_splits: int = 0):
+    """One ebn_npa_target_rank_f32 call on device tensors: the operands of ``npa_topk``, target_pos and window as for ``target_rank``
+    -> (rank [U] int32: 1-based place of the target in ``npa_topk``'s order, 0 = not ranked; count [U] int32; score [U] float32:
+    the target's score, -inf where rank is 0); ``flags`` accumulates."""
+    U, F = users.shape
+    n_rows, L, A = Ua_all.shape
+    M = n_rows if cand_rows is None else cand_rows.shape[0]
+    X = 0 if exclude is None else exclude.shape[1]
+    if target_pos.shape != (U,) or target_pos.dtype != torch.int32 or not target_pos.is_contiguous():
+        raise ValueError(f"target_pos must be a contiguous [{U}] int32 tensor, got {tuple(target_pos.shape)} {target_pos.dtype}")
+    if window is not None and (window.shape != (U, 2) or window.dtype != torch.int32 or not window.is_contiguous()):
+        raise ValueError(f"window must be a contiguous [{U}, 2] int32 tensor, got {tuple(window.shape)} {window.dtype}")
+    rank = torch.empty(U, dtype=torch.int32, device=users.device)
+    count = torch.empty(U, dtype=torch.int32, device=users.device)
+    score = torch.empty(U, dtype=torch.float32, device=users.device)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_npa_topk_auto_splits(U, M, L))
+    ws_bytes = int(lib.ebn_npa_target_rank_workspace_bytes(U, max(splits, 1)))  # one range needs it too: the target scores
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=users.device)
+    _hip.call("ebn_npa_target_rank_f32", _hip.ptr(users), _hip.ptr(Q), _hip.ptr(Ua_all), _hip.ptr(Vd_all), n_rows, _hip.ptr(cand_rows), M,
+              _hip.ptr(target_pos), _hip.ptr(window), _hip.ptr(exclude), X, 1 if sigmoid else 0, splits, _hip.ptr(rank), _hip.ptr(count),
+              _hip.ptr(score), _hip.ptr(flags), _hip.ptr(ws), ws.numel(), U, L, F, A, _hip.stream_handle())
     return rank, count, score
 
 
@@ -468,6 +500,15 @@ def rank_targets(model, loader, targets=None, candidate_ids=None, exclude_histor
     if getattr(model, "_recommend_topk", None) is not None:
         raise NotImplementedError(f"rank_targets is not supported for {type(model).__name__}: its scoring launch has no counting form")
     _check_window(model, window)
+    return _rank_targets(model, loader, targets, candidate_ids, exclude_history, window, scores, users_per_call)
+
+
+def _rank_targets(model, loader, targets=None, candidate_ids=None, exclude_history=True, window=None, scores="sigmoid",
+                  users_per_call=65536, model_launch=None) -> TargetRanks:
+    """The body of ``rank_targets``.  ``model_launch(cache, users, cand_rows, target_pos, window, exclude, sigmoid, flags)`` ->
+    (rank, count, score) is the model's own counting launch (``NPAModel._rank_launch``), or None: ``target_rank`` over act(user . news)."""
+    if window is not None and not isinstance(window, Freshness):
+        raise ValueError(f"window must be None or a Freshness(published, max_age, min_age), got {type(window).__name__}")
     _check(model, loader, 1, scores)
     index = model._recommend_index(loader)
     cand_ids, rows = candidate_rows(index, candidate_ids)
@@ -496,7 +537,10 @@ def rank_targets(model, loader, targets=None, candidate_ids=None, exclude_histor
     def run(u, hh, wd, first, perm):
         tp = target_of_launch.pop()
         tp = (tp if perm is None else tp[perm]).contiguous()
-        return target_rank(u, news_all, cand_d, tp, wd, hh if exclude_history else None, sigmoid, flags)
+        ex = hh if exclude_history else None
+        if model_launch is not None:
+            return model_launch(cache, u, cand_d, tp, wd, ex, sigmoid, flags)
+        return target_rank(u, news_all, cand_d, tp, wd, ex, sigmoid, flags)
 
     outs = _launch_batches(model, cache, loader, device, exclude_history, exclude_history, win_all, users_per_call, run, repeat=repeat)
     cat = lambda k, dtype: (torch.cat([o[k] for o in outs]).cpu().numpy() if outs else np.zeros(0, dtype))

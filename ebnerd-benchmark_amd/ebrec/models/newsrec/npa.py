@@ -15,7 +15,10 @@ Inputs are ``(user_indexes (B,1), his_input_title (B,H,T), pred_input_title (B,C
     catalogue above ``NPAModel.catalogue_max_bytes`` takes it too;
   * ``recommend_pairwise(loader, candidate_ids, top_n=...)`` gives each impression's top-N of one shared candidate list from the
     same once-encoded catalogue: NPA has no per-article vector, so ``ebn_npa_topk_score_f32`` computes every (user, candidate)
-    pair's logits and dots on the matrix cores, pools and selects in one launch (``_recommend.py``); ``recommend`` still raises.
+    pair's logits and dots on the matrix cores, pools and selects in one launch (``_recommend.py``); ``recommend`` still raises;
+  * ``rank_targets_pairwise(loader, targets, candidate_ids, ...)`` is the accuracy side of those lists: the place of each clicked
+    article among all candidates, from ``ebn_npa_target_rank_f32`` -- the same step with a count in place of the selection, also
+    inside ``window=Freshness(...)``; ``rank_targets`` still raises.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ import torch
 
 from ._engine_npa import NPAEngine
 from ._keras_like import ModelBase
-from ._recommend import npa_topk, recommend
+from ._recommend import TargetRanks, _rank_targets, npa_target_rank, npa_topk, recommend
 
 
 class NPAModel(ModelBase):
@@ -119,6 +122,24 @@ class NPAModel(ModelBase):
         errors as the other models' ``recommend``), every (user, candidate) pair scored by personalised pooling from the
         once-encoded catalogue."""
         return recommend(self, loader, candidate_ids, **kwargs)
+
+    # -- the accuracy side of the same lists: ``rank_targets`` still raises, ``rank_targets_pairwise`` does the work ----------------
+    def _rank_launch(self, cache, users, cand_rows, target_pos, window, exclude, sigmoid, flags):
+        """The counting launch of ``_recommend._rank_targets`` for rows ``user_vec | Qn``: ebn_npa_target_rank_f32."""
+        F = self._engine.F
+        return npa_target_rank(users[:, :F].contiguous(), users[:, F:].contiguous(), cache.Ua_all, cache.Vd_all, cand_rows, target_pos,
+                               window, exclude, sigmoid, flags)
+
+    def rank_targets_pairwise(self, loader, targets=None, candidate_ids=None, **kwargs) -> TargetRanks:
+        """Where each impression's clicked article stands among ALL of ``candidate_ids`` (``_recommend.rank_targets``: the same
+        arguments, defaults, results and errors as the other models' ``rank_targets``, ``window=Freshness(...)`` included), every
+        (user, candidate) pair scored by personalised pooling from the once-encoded catalogue and counted in the same launch
+        (``ebn_npa_target_rank_f32``).  The rule: ``rank`` r <= k holds exactly when ``recommend_pairwise(loader, candidate_ids,
+        top_n=k, exclude_history=...)`` has the target at index r - 1, and ``score`` is that slot's score, bit for bit.  Windowed
+        top-N lists for NPA do not exist yet (``recommend_pairwise(..., window=...)`` raises), so under ``window=`` the ranks have
+        no list to be compared with: they follow the same rule inside each impression's window.  A catalogue above
+        ``catalogue_max_bytes`` raises, as it does for ``recommend_pairwise``."""
+        return _rank_targets(self, loader, targets, candidate_ids, model_launch=self._rank_launch, **kwargs)
 
     def train_step(self, user, his, pred, y):
         """One optimizer step on raw arrays; returns the batch loss (device tensor)."""

@@ -1087,6 +1087,39 @@ int ebn_npa_topk_score_f32(const float* users, const float* Q, const float* Ua_a
                            int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace,
                            int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A, ebn_stream_t stream);
 
+/* ---- full-catalogue rank of one target candidate per user for NPA (the accuracy side of the same workflow for npa.py: where the
+ * clicked article stands among all candidates NPA's top-N is drawn from) --------------------------------------------------------------
+ * The counting form of ebn_npa_topk_score_f32, as ebn_target_rank_f32 is the counting form of ebn_topk_score_f32.  Everything not
+ * said here is one of those two contracts.
+ * ebn_npa_topk_score_f32's: the operands (users [U, F], Q [U, A], Ua_all [n_rows, L, A], Vd_all [n_rows, L, F]) and the pair score,
+ * cand_rows == NULL, duplicate rows being distinct candidates, exclude [U, X] matching by catalogue row (-1 and rows past the table
+ * match nothing), padded tokens (weight 0, never read), the limits (1 <= L <= 64, A % 4 == 0, 4 <= A <= 1024, F % 4 == 0,
+ * 4 <= F <= 4096, X <= 256: EBN_ERR_UNSUPPORTED; users / Q / Ua_all / Vd_all 16-byte aligned: EBN_ERR_ALIGN) and the steps n_splits
+ * divides (0 = ebn_npa_topk_auto_splits(U, M, L); with windows: the steps a workgroup's windows meet).
+ * ebn_target_rank_f32's: target_pos [U] (required; < 0: no target; >= M: no target and flags[0]), window [U, 2] and its clamping
+ * (NULL: every position is inside), out_rank / out_count / out_score and mode, M == 0 (rank 0, count 0, score -inf), flags[0] and
+ * flags[1] including the either-value clause for a row outside the table that lies inside a workgroup's span but in nobody's
+ * window, the argument codes (all checked on the host before anything is launched: a failing call writes nothing), U == 0 (nothing
+ * to do), no atomics on global memory.
+ * s(u, c) and the target's score t have the BITS ebn_npa_topk_score_f32 gives the same (user rows, catalogue row) pair: the same fma
+ * chains, in-lane reduction order, cross-half add and division.  Position c is admissible for user u when it lies in u's clamped
+ * window, cand_rows[c] lies in [0, n_rows) and is not in exclude[u, :], and s(u, c) is not NaN.  out_count[u] is the number of
+ * admissible positions; out_rank[u] is 1 + the number of admissible positions ahead of the target in ebn_npa_topk_score_f32's order
+ * (score descending, then position ascending), or 0 when the target is absent or inadmissible.  So out_rank[u] = r <= k holds
+ * exactly when ebn_npa_topk_score_f32 with the same exclude and k has the target at index r - 1, and out_score[u] is then that
+ * slot's score, bit for bit.  The three outputs depend neither on n_splits, nor on the run, nor on which other users share the launch.
+ * Three launches: a target pass (t [U] into the workspace), the walk (two partial counts per user and range into the workspace), a
+ * small one that adds them and writes the outputs.  So ONE range needs the workspace too: 16-byte aligned, at least
+ * ebn_npa_target_rank_workspace_bytes(U, n_splits) bytes (n_splits 0: that of ebn_npa_topk_auto_splits), else EBN_ERR_BAD_ARG.      */
+/* Bytes of workspace for n_splits >= 1 candidate ranges; 0 for sizes outside the limits, never negative.  Pure host query.         */
+int64_t ebn_npa_target_rank_workspace_bytes(int64_t n_users, int32_t n_splits);
+int ebn_npa_target_rank_f32(const float* users, const float* Q, const float* Ua_all, const float* Vd_all, int64_t n_rows,
+                            const int32_t* cand_rows, int64_t M, const int32_t* target_pos, const int32_t* window,
+                            const int32_t* exclude, int32_t X, int32_t mode, int32_t n_splits,
+                            int32_t* out_rank, int32_t* out_count, float* out_score, int32_t* flags,
+                            void* workspace, int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A,
+                            ebn_stream_t stream);
+
 /* ---- MMR re-ranking of a relevance pool (greedy Maximal Marginal Relevance over the distance of IntralistDiversity,
  * beyond_accuracy.py:81-96: the list a top-N of ebn_topk_score_f32 with k = P becomes when relevance is traded against diversity) ---
  * Per user u of U: P pool entries, relevance pool_rel[u, i] and row pool_rows[u, i] of the UNIT table unit [n_rows, D] (what
