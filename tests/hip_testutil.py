@@ -65,13 +65,17 @@ def assert_close(got, want, rtol=1e-5, atol=1e-6, what=""):
     got = np.asarray(got, dtype=np.float64)
     want = np.asarray(want, dtype=np.float64)
     assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = np.abs(got - want)
-    tol = atol + rtol * np.abs(want)
-    bad = err > tol
+    with np.errstate(invalid="ignore"):
+        err = np.abs(got - want)
+        tol = atol + rtol * np.abs(want)
+        bad = ~(err <= tol)  # not `err > tol`: that is false for a NaN in `got`
     if bad.any():
-        i = np.unravel_index(np.argmax(err - tol), err.shape)
-        raise AssertionError(f"{what}: {bad.sum()}/{bad.size} elements off; worst at {i}: got {got[i]!r} want "
-                             f"{want[i]!r} (abs err {err[i]:.3e}, tol {tol[i]:.3e}); max abs err {err.max():.3e}")
+        over = np.where(np.isfinite(err), err - tol, np.inf)  # a NaN / inf counts as the worst element
+        i = np.unravel_index(np.argmax(over), err.shape)
+        finite = err[np.isfinite(err)]
+        raise AssertionError(f"{what}: {bad.sum()}/{bad.size} elements off ({int(np.isnan(got).sum())} NaN); worst at {i}: got {got[i]!r} want "
+                             f"{want[i]!r} (abs err {err[i]:.3e}, tol {tol[i]:.3e}); max finite abs err "
+                             f"{finite.max() if finite.size else float('nan'):.3e}")
 
 
 class ReluTieGate:

@@ -10,17 +10,10 @@ import torch
 from oracle import nrms_numpy as on
 from tests import npa_oracle as npo
 from tests.hip_testutil import P, S, assert_close, dev, host, make_state
+from tests.model_kernel_refs import SEED, STEP, _mult
 from tests.test_data_pipeline import frames  # noqa: F401  (the fixture of the reference loader test)
 
 pytestmark = pytest.mark.gpu
-
-SEED, STEP = 21, 3
-
-
-def _mult(site, p, n):
-    if p <= 0:
-        return np.ones(n)
-    return on.dropout_keep_mask(on.dropout_key(SEED, STEP, site), n, p) / (1.0 - p)
 
 
 def _unfold(X, T, window):
