@@ -10,21 +10,16 @@
 // order.  Dropout uses the counter stream of ebn_common.h; the key of a call site travels BY VALUE in the call (the module derives it
 // from its seed, its own step counter and the site number), so ebn_step_state is not involved.
 #include "ebn_common.h"
+#include "ebn_ff_attn.h"
 #include "ebn_reduce.h"
 
 namespace {
 
-constexpr int FF_THREADS = 256;
-constexpr int FF_WAVES = FF_THREADS / 64;
 constexpr int FF_LN_MAX_D = 1024;      // LayerNorm backward keeps 4 waves x 3 column accumulators of D floats in LDS (48 KiB)
 constexpr int FF_MAX_PARTS = 512;      // workgroups (= partials) of a LayerNorm backward
-constexpr int FF_ATT_MAX_PARTS = 256;  // workgroups (= partials) of the attention backward
 constexpr int FF_ATT_ACC = 16;         // logit-weight gradient elements a thread keeps: heads * D <= 256 * 16
-constexpr int FF_ATT_MAX_D = 1024;     // 4 column sums per thread
-constexpr int FF_LDS_BYTES = 64 * 1024;
 constexpr int FF_POOL_MAX_L = 4096;
 constexpr float FF_POOL_EPS = 1e-8f;   // fastformer.py AttentionPooling.forward
-constexpr float FF_MASK_NEG = -10000.0f;
 
 struct FfDrop {
   uint32_t key, thresh;
@@ -312,58 +307,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_head_bwd_kernel(const float* __
   }
 }
 
-// ---- fast additive attention core -------------------------------------------------------------------------------------------------
-struct FfAttn {
-  float* Q;           // [n_seq*T, D] in: x.Wq^T, out: + bq (mixed_query_layer)
-  float* K;           // likewise with bk
-  const float* bq;
-  const float* bk;
-  const float* btr;   // transform.bias (only with SV0)
-  const float* Wqa;   // [heads, D]
-  const float* bqa;   // [heads]
-  const float* Wka;
-  const float* bka;
-  const float* mask;  // [n_seq, T] 1 = token, 0 = padding
-  float* AO;          // [n_seq*T, D] pooled_key * Q
-  float* SV0;         // [n_seq*T, D] Q + btr, or NULL
-  float* qw;          // [n_seq, heads, T]
-  float* kw;
-  float* pq;          // [n_seq, D]
-  float* pk;
-  // backward
-  const float* dAO;
-  const float* dSV;   // gradient reaching Q through "+ mixed_query_layer", or NULL
-  float* dQ;
-  float* dK;
-  float* partials;    // [grid][2 * heads * D + 3 * D]
-  int64_t n_seq;
-  int32_t T, D, heads;
-  float inv;          // 1 / sqrt(head size)
-};
-
-// softmax over the T logits of each head, in place in LDS and out to global; wave per head
-__device__ __forceinline__ void ff_softmax_rows(float* sw, float* __restrict__ gout, int T, int H) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int h = wave; h < H; h += FF_WAVES) {
-    float* row = sw + h * T;
-    float m = -INFINITY;
-    for (int t = lane; t < T; t += 64) m = fmaxf(m, row[t]);
-    m = ebn_wave_max(m);
-    float s = 0.f;
-    for (int t = lane; t < T; t += 64) {
-      const float e = expf(row[t] - m);
-      row[t] = e;
-      s += e;
-    }
-    s = ebn_wave_sum(s);
-    for (int t = lane; t < T; t += 64) {
-      const float p = row[t] / s;
-      row[t] = p;
-      gout[h * T + t] = p;
-    }
-  }
-}
-
+// ---- fast additive attention core (FfAttn and the softmax routines: ebn_ff_attn.h) ------------------------------------------------
 // logits of one LDS row against the [heads, D] weight: every head reads the WHOLE row
 __device__ __forceinline__ void ff_row_logits(const float* row, const float* __restrict__ Wa, const float* __restrict__ ba, float* sw,
                                               int t, int T, int D, int H, float inv, float maskterm) {
@@ -465,17 +409,6 @@ __global__ __launch_bounds__(FF_THREADS) void ff_attn_fwd_kernel(FfAttn a) {
     const float4 q = *reinterpret_cast<const float4*>(sq + t * ldq + c);
     const float4 p = *reinterpret_cast<const float4*>(spk + c);
     *reinterpret_cast<float4*>(a.AO + base + t * D + c) = make_float4(q.x * p.x, q.y * p.y, q.z * p.z, q.w * p.w);
-  }
-}
-
-// softmax backward per head in LDS: sd <- p * (sd - sum_t p sd); wave per head
-__device__ __forceinline__ void ff_softmax_bwd_rows(const float* sp, float* sd, int T, int H) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int h = wave; h < H; h += FF_WAVES) {
-    float s = 0.f;
-    for (int t = lane; t < T; t += 64) s = fmaf(sp[h * T + t], sd[h * T + t], s);
-    s = ebn_wave_sum(s);
-    for (int t = lane; t < T; t += 64) sd[h * T + t] = sp[h * T + t] * (sd[h * T + t] - s);
   }
 }
 
@@ -659,8 +592,6 @@ int ff_attn_check(int64_t n_seq, int32_t T, int32_t D, int32_t heads, bool bwd) 
   EBN_REQUIRE(ebn_sat_mul(ebn_sat_mul(n_seq, T), D) < (int64_t(1) << 40), EBN_ERR_UNSUPPORTED);
   return EBN_OK;
 }
-
-int64_t ff_attn_grid(int64_t n_seq) { return n_seq < FF_ATT_MAX_PARTS ? (n_seq < 1 ? 1 : n_seq) : FF_ATT_MAX_PARTS; }
 
 int ff_pool_check(int64_t n_seq, int32_t L, int32_t D) {
   EBN_REQUIRE(n_seq >= 0 && L > 0 && D > 0, EBN_ERR_BAD_ARG);

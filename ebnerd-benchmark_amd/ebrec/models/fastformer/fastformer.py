@@ -22,7 +22,17 @@ embedding dropout, sites ``1 + 2 l`` and ``2 + 2 l`` the two dropouts of layer `
 (``dropout_step``, advanced by every training-mode forward).  The logit biases ``query_att.bias`` / ``key_att.bias`` have
 identically zero gradients (a softmax does not see a shift of its logits) and get exact zeros.
 
-Limits of the autograd Function: the backward reads the parameters themselves and releases (and partly overwrites) the saved
+The attention core has two kernel pairs (keyword-only ``attention``):
+
+* ``"resident"`` (default) keeps a sequence's Q rows in LDS: ``heads * hidden_size <= 4096`` and 64 KiB of LDS for ``T * (hidden_size
+  + 4)`` floats plus the rest, i.e. hidden 256 / 16 heads with at most 47 tokens per title when training;
+* ``"streamed"`` (``csrc/ebn_fastformer_streamed.hip``) re-reads Q and K from global memory and leaves the logit weights' gradients
+  to the split-K GEMM: ``hidden_size <= 1024`` with any number of heads, LDS ``4 * (heads * T + T + 2 * hidden_size)`` bytes forward
+  and ``4 * (2 * heads * T + 4 * hidden_size)`` backward (hidden 768 / 12 heads: 554 tokens when training);
+* ``"auto"`` takes the resident pair wherever it accepts the shape (for both directions when the forward keeps activations) -- then
+  bit-identical to the default -- and the streamed pair otherwise.
+
+The option changes no parameter.  Limits of the autograd Function: the backward reads the parameters themselves and releases (and partly overwrites) the saved
 activations, so a parameter changed in place between forward and backward, or a second backward through the same forward
 (``retain_graph=True``), raises ``RuntimeError``.  The shape rules of both directions are checked at the start of a forward that
 keeps activations.  An eager step synchronises with the host twice (the out-of-range flags of the gather and of the fixed-point
@@ -31,12 +41,14 @@ scatter).
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 from torch import nn
 
 _M32 = 0xFFFFFFFF
 TOKEN_MASKS = ("first_slot", "per_slot")
+ATTENTIONS = ("resident", "streamed", "auto")
 
 
 def _lowbias32(x: int) -> int:
@@ -139,12 +151,18 @@ class _Engine:
         if rc == -2:
             shape = (f"hidden_size = {self.D}, heads = {self.heads}, intermediate_size = {self.I}, tokens per title = "
                      f"{getattr(self, 'T', '?')}")
+            if name.startswith("ebn_ff_attn_streamed"):
+                raise ValueError(
+                    f"{name}: shape outside what the streamed Fastformer attention kernels are built for ({shape}).  Limits: hidden_size % 4 "
+                    "== 0, hidden_size <= 1024, T <= 4096, and per sequence 4 * (heads * T + T + 2 * hidden_size) bytes (forward) and 4 * (2 * "
+                    "heads * T + 4 * hidden_size) bytes (backward) <= 64 KiB of LDS")
             if name.startswith("ebn_ff_attn"):
                 raise ValueError(
                     f"{name}: shape outside what the Fastformer attention kernels are built for ({shape}).  Limits: hidden_size % 4 == 0, "
                     "hidden_size <= 1024, heads * hidden_size <= 4096, and per sequence 4 * (T * (hidden_size + 4) + 6 * hidden_size + "
                     "heads * T + T) bytes (forward) and 4 * (T * (hidden_size + 4) + 4 * hidden_size + 4 * heads * T) bytes (backward) "
-                    "<= 64 KiB of LDS")
+                    "<= 64 KiB of LDS.  Fastformer(..., attention=\"auto\") takes the streamed kernels, which keep no sequence in LDS, for "
+                    "such shapes")
             raise ValueError(f"{name}: shape outside the kernel's supported range ({shape}); LayerNorm needs hidden_size <= 1024, "
                              "the pooling a history size <= 4096 (see include/ebnerd_hip.h)")
         if rc != 0:
@@ -167,8 +185,8 @@ class _Engine:
         self.call("ebn_gemm_f32", 0, 0, dy.shape[0], n_in, n_out, _f(1), ptr(dy), n_out, ptr(W), n_in, _f(beta), ptr(out), n_in, stream_handle())
         return out
 
-    def back_weight(self, dy, x):
-        """dW [n_out, n_in] = dy^T . x with deterministic split-K over the rows."""
+    def back_weight(self, dy, x, alpha=1.0):
+        """dW [n_out, n_in] = alpha * dy^T . x with deterministic split-K over the rows."""
         from ebrec import _hip
         from ebrec._hip import ptr, stream_handle
 
@@ -178,7 +196,7 @@ class _Engine:
         if ws is None:
             ws = self._ws[(dy.device, n_ws)] = torch.empty(max(n_ws, 1), device=dy.device)
         dW = torch.empty(n_out, n_in, device=dy.device)
-        self.call("ebn_gemm_f32_ws", 1, 0, n_out, n_in, R, _f(1), ptr(dy), n_out, ptr(x), n_in, _f(0), ptr(dW), n_in, ptr(ws), n_ws, stream_handle())
+        self.call("ebn_gemm_f32_ws", 1, 0, n_out, n_in, R, _f(alpha), ptr(dy), n_out, ptr(x), n_in, _f(0), ptr(dW), n_in, ptr(ws), n_ws, stream_handle())
         return dW
 
     def finish(self, partials, n_parts, stride, width):
@@ -244,6 +262,18 @@ class _Engine:
             grads[prefix + "att_fc1.weight"] = self.back_weight(U, X)
         self.back_data(U, pool.att_fc1.weight, dX, beta=1.0)
 
+    def attention_kind(self, T, keep):
+        """"resident" or "streamed" for sequences of T tokens, by the model's `attention` option; raises ValueError with the limits of
+        the pair it settles on when that pair does not take the shape (both directions when `keep`: a training step must not learn its
+        limit inside loss.backward())."""
+        from ebrec import _hip
+
+        want, both = self.m.attention, 1 if keep else 0
+        if want == "auto":
+            want = "resident" if _hip.lib().ebn_ff_attn_supported(T, self.D, self.heads, both) == 0 else "streamed"
+        self.call("ebn_ff_attn_supported" if want == "resident" else "ebn_ff_attn_streamed_supported", T, self.D, self.heads, both)
+        return want
+
     # -- the model
     def masks(self, hist, cand, token_mask):
         N, H, T = hist.shape
@@ -270,7 +300,8 @@ class _Engine:
         mask, hmask = self.masks(hist, cand, token_mask)
         S = stream_handle
         # both directions' shape rules before anything runs: a training step must not learn its limit inside loss.backward()
-        self.call("ebn_ff_attn_supported", T, D, heads, 1 if keep else 0)
+        kind = self.attention_kind(T, keep)
+        attn_fwd = "ebn_ff_attn_fwd_f32" if kind == "resident" else "ebn_ff_attn_streamed_fwd_f32"
         X0 = torch.empty(R, E, device=dev)
         oob = torch.zeros(1, dtype=torch.int32, device=dev)
         self.call("ebn_gather_rows_f32", ptr(ids), ptr(table), ptr(X0), R, E, V, None, -1, _f(0), ptr(oob), S())
@@ -286,7 +317,7 @@ class _Engine:
             AO, SV = torch.empty(R, D, device=dev), torch.empty(R, D, device=dev)
             qw, kw = torch.empty(n_seq, heads, T, device=dev), torch.empty(n_seq, heads, T, device=dev)
             pq, pk = torch.empty(n_seq, D, device=dev), torch.empty(n_seq, D, device=dev)
-            self.call("ebn_ff_attn_fwd_f32", ptr(Q), ptr(K), ptr(at.query.bias), ptr(at.key.bias), ptr(at.transform.bias), ptr(at.query_att.weight),
+            self.call(attn_fwd, ptr(Q), ptr(K), ptr(at.query.bias), ptr(at.key.bias), ptr(at.transform.bias), ptr(at.query_att.weight),
                       ptr(at.query_att.bias), ptr(at.key_att.weight), ptr(at.key_att.bias), ptr(mask), ptr(AO), ptr(SV), ptr(qw), ptr(kw),
                       ptr(pq), ptr(pk), n_seq, T, D, heads, S())
             self.linear(AO, at.transform.weight, SV, beta=1.0)  # SV = transform(AO) + mixed_query_layer
@@ -314,7 +345,7 @@ class _Engine:
         saved = None
         if keep:
             saved = dict(N=N, H=H, T=T, ids=ids, X0=X0, xhat0=xhat0, rstd0=rstd0, layers=saved_layers, hL=h, NV=NV, sv_tok=sv_tok,
-                         user=user, sv_user=sv_user, score=score, p=p, keys=keys)
+                         user=user, sv_user=sv_user, score=score, p=p, keys=keys, attention=kind)
         return score, saved, (user, NV)
 
     def backward(self, sv, dscore, need):
@@ -370,16 +401,30 @@ class _Engine:
                 g[pre + "attention.self.transform.weight"] = self.back_weight(dSV, AO)
             dAO = self.back_data(dSV, at.transform.weight, dY1)  # dY1's buffer is free again
             dQ, dK = torch.empty(R, D, device=dev), torch.empty(R, D, device=dev)
-            width = 2 * heads * D + 3 * D
-            part = torch.empty(int(_hip.lib().ebn_ff_attn_partials_len(n_seq, D, heads)), device=dev)
             n = ctypes.c_int32(0)
-            self.call("ebn_ff_attn_bwd_f32", ptr(Q), ptr(K), ptr(at.query_att.weight), ptr(at.key_att.weight), ptr(qw), ptr(kw), ptr(pq), ptr(pk),
-                      ptr(dAO), ptr(dSV), ptr(dQ), ptr(dK), ptr(part), ctypes.byref(n), n_seq, T, D, heads, S())
-            s = self.finish(part, n.value, width, width)
-            HD = heads * D
             a = pre + "attention.self."
-            g[a + "query_att.weight"], g[a + "key_att.weight"] = s[:HD].view(heads, D), s[HD:2 * HD].view(heads, D)
-            g[a + "query.bias"], g[a + "key.bias"], g[a + "transform.bias"] = s[2 * HD:2 * HD + D], s[2 * HD + D:2 * HD + 2 * D], s[2 * HD + 2 * D:]
+            if sv["attention"] == "resident":
+                width = 2 * heads * D + 3 * D
+                part = torch.empty(int(_hip.lib().ebn_ff_attn_partials_len(n_seq, D, heads)), device=dev)
+                self.call("ebn_ff_attn_bwd_f32", ptr(Q), ptr(K), ptr(at.query_att.weight), ptr(at.key_att.weight), ptr(qw), ptr(kw), ptr(pq), ptr(pk),
+                          ptr(dAO), ptr(dSV), ptr(dQ), ptr(dK), ptr(part), ctypes.byref(n), n_seq, T, D, heads, S())
+                s = self.finish(part, n.value, width, width)
+                HD = heads * D
+                g[a + "query_att.weight"], g[a + "key_att.weight"] = s[:HD].view(heads, D), s[HD:2 * HD].view(heads, D)
+                s = s[2 * HD:]
+            else:  # the streamed pair leaves the logit gradients and the K * pooled_query rows: the logit weights' gradients are GEMMs
+                lib = _hip.lib()
+                part = torch.empty(int(lib.ebn_ff_attn_streamed_partials_len(n_seq, D)), device=dev)
+                n_dl = int(lib.ebn_ff_attn_streamed_dlogits_len(n_seq, T, heads))
+                d1, d2 = torch.empty(n_dl, device=dev).view(R, heads), torch.empty(n_dl, device=dev).view(R, heads)
+                KP = torch.empty(int(lib.ebn_ff_attn_streamed_kp_len(n_seq, T, D)), device=dev).view(R, D)
+                self.call("ebn_ff_attn_streamed_bwd_f32", ptr(Q), ptr(K), ptr(at.query_att.weight), ptr(at.key_att.weight), ptr(qw), ptr(kw), ptr(pq),
+                          ptr(pk), ptr(dAO), ptr(dSV), ptr(dQ), ptr(dK), ptr(d1), ptr(d2), ptr(KP), ptr(part), ctypes.byref(n), n_seq, T, D, heads, S())
+                s = self.finish(part, n.value, 3 * D, 3 * D)
+                inv = 1.0 / math.sqrt(D // heads)
+                g[a + "query_att.weight"], g[a + "key_att.weight"] = self.back_weight(d1, Q, inv), self.back_weight(d2, KP, inv)
+                del d1, d2, KP
+            g[a + "query.bias"], g[a + "key.bias"], g[a + "transform.bias"] = s[:D], s[D:2 * D], s[2 * D:]
             g[a + "query_att.bias"] = torch.zeros(heads, device=dev)
             g[a + "key_att.bias"] = torch.zeros(heads, device=dev)
             if need(a + "query.weight"):
@@ -449,7 +494,8 @@ class Fastformer(nn.Module):
     ``num_hidden_layers``, ``intermediate_size``, ``max_position_embeddings``, ``hidden_dropout_prob``, ``layer_norm_eps``,
     ``initializer_range``, ``hidden_act``, ``pooler_type``, ``vocab_size``."""
 
-    def __init__(self, config, word_embedding: nn.Embedding = None, *, token_mask: str = "first_slot", seed: int = 0):
+    def __init__(self, config, word_embedding: nn.Embedding = None, *, token_mask: str = "first_slot", seed: int = 0,
+                 attention: str = "resident"):
         super().__init__()
         if getattr(config, "hidden_act", "gelu") != "gelu":
             raise ValueError(f"hidden_act = {config.hidden_act!r}: only 'gelu' (the exact erf form) has a kernel")
@@ -457,8 +503,11 @@ class Fastformer(nn.Module):
             raise ValueError(f"pooler_type = {config.pooler_type!r}: only 'weightpooler' is supported")
         if token_mask not in TOKEN_MASKS:
             raise ValueError(f"token_mask = {token_mask!r}: one of {TOKEN_MASKS}")
+        if attention not in ATTENTIONS:
+            raise ValueError(f"attention = {attention!r}: one of {ATTENTIONS}")
         self.config = config
         self.token_mask = token_mask
+        self.attention = attention
         self.seed = int(seed)
         self.dropout_step = 0
         self.word_embedding = nn.Embedding(config.vocab_size, config.hidden_size) if word_embedding is None else word_embedding

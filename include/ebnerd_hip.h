@@ -825,6 +825,34 @@ int ebn_ff_attn_supported(int32_t T, int32_t D, int32_t heads, int32_t with_back
 int ebn_ff_attn_bwd_f32(const float* Q, const float* K, const float* Wqa, const float* Wka, const float* qw, const float* kw,
                         const float* pq, const float* pk, const float* dAO, const float* dSV, float* dQ, float* dK, float* partials,
                         int32_t* n_parts, int64_t n_seq, int32_t T, int32_t D, int32_t heads, ebn_stream_t stream);
+/* The streamed pair (csrc/ebn_fastformer_streamed.hip): the same operation for shapes the pair above refuses -- hidden 768 / 12
+ * heads, hidden 1024 / 16 heads, hundreds of tokens.  Nothing T x D is kept in LDS: a token row lives in the registers of the wave
+ * that works on it and Q, K are re-read from global memory.  ebn_ff_attn_streamed_fwd_f32 takes the arguments of
+ * ebn_ff_attn_fwd_f32 and leaves the same tensors, the biased Q and K included.
+ * Shape rules: D % heads == 0 (else EBN_ERR_BAD_ARG); D % 4 == 0, D <= 1024, T <= 4096, any heads <= D (heads * D is not bounded),
+ * and 4 * (heads * T + T + 2 * D) bytes of LDS <= 64 KiB forward, 4 * (2 * heads * T + 4 * D) backward (EBN_ERR_UNSUPPORTED):
+ * T <= 1142 forward and T <= 554 backward at D = 768, 12 heads.  Q, K, AO, SV0, kp and the weights 16-byte aligned.
+ * ebn_ff_attn_streamed_supported is the pure host query of these rules, as ebn_ff_attn_supported is of the resident pair's.    */
+int ebn_ff_attn_streamed_supported(int32_t T, int32_t D, int32_t heads, int32_t with_backward);
+int ebn_ff_attn_streamed_fwd_f32(float* Q, float* K, const float* bq, const float* bk, const float* btr, const float* Wqa,
+                                 const float* bqa, const float* Wka, const float* bka, const float* mask, float* AO, float* SV0,
+                                 float* qw, float* kw, float* pq, float* pk, int64_t n_seq, int32_t T, int32_t D, int32_t heads,
+                                 ebn_stream_t stream);
+/* Its backward: dQ, dK as above; *n_parts (HOST out-parameter, <= 256) per-workgroup partials [n_parts][3 * D] = colsum(dQ) |
+ * colsum(dK) | colsum(dSV) for ebn_ff_colsum_finish_f32 (workgroup g walks the sequences g, g + n_parts, ...).  The logit-weight
+ * gradients are NOT formed here: the kernel writes d1, d2 [n_seq*T, heads], the gradients of the query / key logits behind their
+ * softmax backwards, and kp [n_seq*T, D] = K * pq, and the caller computes
+ *   dWqa [heads, D] = inv * d1^T . Q,   dWka = inv * d2^T . kp,   inv = 1 / sqrt(D / heads)
+ * with ebn_gemm_f32_ws(transA = 1, transB = 0, heads, D, n_seq*T, inv, ...).  Sizes in floats: partials
+ * ebn_ff_attn_streamed_partials_len(n_seq, D), d1 and d2 ebn_ff_attn_streamed_dlogits_len(n_seq, T, heads) each, kp
+ * ebn_ff_attn_streamed_kp_len(n_seq, T, D); every element of all four is written.                                                */
+int64_t ebn_ff_attn_streamed_partials_len(int64_t n_seq, int32_t D);
+int64_t ebn_ff_attn_streamed_dlogits_len(int64_t n_seq, int32_t T, int32_t heads);
+int64_t ebn_ff_attn_streamed_kp_len(int64_t n_seq, int32_t T, int32_t D);
+int ebn_ff_attn_streamed_bwd_f32(const float* Q, const float* K, const float* Wqa, const float* Wka, const float* qw,
+                                 const float* kw, const float* pq, const float* pk, const float* dAO, const float* dSV, float* dQ,
+                                 float* dK, float* d1, float* d2, float* kp, float* partials, int32_t* n_parts, int64_t n_seq,
+                                 int32_t T, int32_t D, int32_t heads, ebn_stream_t stream);
 
 /* Step prologue: copy up to three device buffers (history ids, candidate ids, labels of a batch handed over as device
  * tensors -- the inputs of nrms.py:170-176) into the step's static buffers with ONE launch; n_i in bytes, multiples

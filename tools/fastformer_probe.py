@@ -1,14 +1,15 @@
-"""Times one Fastformer training step at the ff-c1 shape on one GPU, and the same step of the float32 torch oracle.
+"""Times one Fastformer training step at the ff-c1 or the ff-bert shape on one GPU, and the same step of the float32 torch oracle.
 
 ff-c1: 32000 x 300 trainable word table, hidden 256, 16 heads, 2 layers, intermediate 256, dropout 0.2, T = 30 tokens, H = 20
 history slots, 32 impressions x 5 candidates = 160 (history, candidate) pairs per step, torch.optim.Adam.  The history is repeated
-per candidate, as the reference's dataset does.  A step is forward + BCELoss + backward + optimizer step, eager (no graph), timed
+per candidate, as the reference's dataset does.  ff-bert: hidden 768, 12 heads, everything else as ff-c1 (a shape only the
+streamed attention pair takes: --attention streamed or auto).  A step is forward + BCELoss + backward + optimizer step, eager (no graph), timed
 between two HIP events after warm-up.  Static FLOP count of the GEMMs of a step (R = 160 * 21 * 30 token rows; forward, data and
 weight gradient each 2 R K N): 3 * 2 R (E D + layers (5 D D + 2 D I) + D D) with the pooler's att_fc1 as the last term.
 The oracle (tests/fastformer_oracle.py, float32, autograd, torch's own dropout-free arithmetic with the same masks multiplied in)
 runs eagerly on the same GPU with the same optimizer.  Prints ONE JSON line.  Per-kernel times come from a separate run under
 `rocprofv3 --kernel-trace --stats -- python tools/fastformer_probe.py --steps 10 --no-oracle`.
-usage: fastformer_probe.py [--steps K] [--warmup W] [--no-oracle]"""
+usage: fastformer_probe.py [--config ff-c1|ff-bert] [--attention resident|streamed|auto] [--steps K] [--warmup W] [--no-oracle]"""
 import argparse
 import json
 import sys
@@ -25,6 +26,7 @@ for p in (str(ROOT), str(ROOT / "ebnerd-benchmark_amd")):
 from ebrec import _hip  # noqa: E402
 
 PEAK_TFLOPS = 157.3  # exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) peak of the MI355X
+CONFIGS = {"ff-c1": (256, 16), "ff-bert": (768, 12)}  # hidden size, heads
 
 
 def events_ms(fn, reps):
@@ -42,17 +44,20 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-oracle", action="store_true")
+    ap.add_argument("--config", choices=sorted(CONFIGS), default="ff-c1")
+    ap.add_argument("--attention", choices=("resident", "streamed", "auto"), default="resident")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     from ebrec.models.fastformer import Fastformer
     from tests import fastformer_oracle as fo
 
-    V, E, D, heads, layers, I, T, H, B, C, p = 32000, 300, 256, 16, 2, 256, 30, 20, 32, 5, 0.2
+    V, E, layers, I, T, H, B, C, p = 32000, 300, 2, 256, 30, 20, 32, 5, 0.2
+    D, heads = CONFIGS[a.config]
     cfg = SimpleNamespace(hidden_size=D, num_attention_heads=heads, num_hidden_layers=layers, intermediate_size=I, max_position_embeddings=512,
                           hidden_dropout_prob=p, layer_norm_eps=1e-12, initializer_range=0.02, hidden_act="gelu", pooler_type="weightpooler",
                           vocab_size=V)
     torch.manual_seed(0)
-    model = Fastformer(cfg, word_embedding=torch.nn.Embedding(V, E), seed=1).cuda().train()
+    model = Fastformer(cfg, word_embedding=torch.nn.Embedding(V, E), seed=1, attention=a.attention).cuda().train()
     rng = np.random.default_rng(0)
     N = B * C
     batches = []
@@ -114,7 +119,7 @@ def main():
 
     R = N * (H + 1) * T
     flop = 3 * 2 * R * (E * D + layers * (5 * D * D + 2 * D * I) + D * D)
-    out = {"what": "fastformer_probe", "config": "ff-c1", "device": torch.cuda.get_device_name(0), "pairs": N, "H": H, "T": T, "V": V, "E": E,
+    out = {"what": "fastformer_probe", "config": a.config, "attention": model._engine.attention_kind(T, True), "device": torch.cuda.get_device_name(0), "pairs": N, "H": H, "T": T, "V": V, "E": E,
            "hidden": D, "heads": heads, "layers": layers, "intermediate": I, "dropout": p, "optimizer": "torch.optim.Adam", "steps": a.steps,
            "warmup": a.warmup, "ms_per_step": round(ms, 4), "pairs_per_s": round(N / ms * 1e3, 1), "gemm_gflop_per_step": round(flop / 1e9, 2),
            "gemm_tflops_over_step": round(flop / ms / 1e9, 2), "fraction_of_fp32_peak": round(flop / ms / 1e9 / PEAK_TFLOPS, 4),
