@@ -16,7 +16,26 @@ left.  ``lam = 1`` is the relevance order of the pool, ``lam = 0`` looks at the 
 Two paths, as in beyond_accuracy.py.  With a `DeviceLookup` that holds the key the pools go through ``ebn_mmr_rerank_f32``
 (csrc/ebn_rerank.hip: the unit rows gathered into LDS, an exact-fp32 MFMA Gram matrix per pool, one wave running the rounds);
 with a plain dict (or a DeviceLookup with ``device=None``) they run in float64 numpy, list by list.  torch is imported only on
-the device path.  ``model.recommend(..., rerank=MMR(...))`` runs the same kernel on the model's own top-``pool``."""
+the device path.  ``model.recommend(..., rerank=MMR(...))`` runs the same kernel on the model's own top-``pool``.
+
+Determinantal point process (DPP), fast greedy MAP inference (Chen, Zhang, Zhou, NeurIPS 2018).
+
+The same pools, absent entries and distance.  MMR scores a pick against its NEAREST earlier pick; DPP scores the whole list through
+log det of its similarity matrix, so an entry inside the span of three earlier picks is penalised though it is close to none.
+
+    S(i, j) = 1 - d(i, j) / 2       (1 + cos) / 2 for unit vectors: positive semi-definite, in [0, 1]; the diagonal as computed
+                                    (1 for a unit vector, 1/2 for a zero vector)
+    state per entry: d2_i, the conditional variance of i given the picks (initially S(i, i)), and a Cholesky row c_i;  EPS = 1e-4
+    round t = 0, 1, ...: pick, among the present entries not yet picked, the largest  lam * score_i + (1 - lam) * log(max(d2_i, EPS))
+    after picking j: if d2_j <= EPS the pick is degenerate (already spanned): c_i[t] = 0 and nothing else changes; otherwise
+        e_i = (S(j, i) - sum_{s<t} c_j[s] c_i[s]) / sqrt(d2_j),   c_i[t] = e_i,   d2_i -= e_i * e_i
+
+larger objective first, equal objectives to the smaller pool index; the rounds end after ``top_n`` picks or when nothing is left.
+lam * score_i is the marginal gain of lam * sum score + (1 - lam) * log det S_Y, so ``lam = 1`` is the relevance order of the pool.
+A pool whose rank is below ``top_n`` still fills its list: spanned entries are clamped at EPS, not dropped, and then order by
+score.  The two paths are MMR's: ``ebn_dpp_rerank_f32`` (csrc/ebn_dpp.hip: the same Gram stage, then one wave per pool running an
+incremental Cholesky with its rows in LDS) or float64 numpy; ``model.recommend(..., rerank=DPP(...))`` runs the kernel on the
+model's own top-``pool``."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -26,7 +45,7 @@ import numpy as np
 from ebrec.evaluation.beyond_accuracy import DeviceLookup, label_lookup
 from ebrec.evaluation.utils import check_key_in_all_nested_dicts
 
-MAX_POOL, MAX_TOP_N = 64, 64  # limits of ebn_mmr_rerank_f32 and ebn_calibrated_rerank_f32 (include/ebnerd_hip.h)
+MAX_POOL, MAX_TOP_N = 64, 64  # limits of ebn_mmr_rerank_f32, ebn_dpp_rerank_f32 and ebn_calibrated_rerank_f32 (include/ebnerd_hip.h)
 MAX_LABELS, MAX_HISTORY = 128, 256  # limits of ebn_calibrated_rerank_f32 / ebn_label_target_f32
 
 
@@ -38,6 +57,20 @@ class MMR:
     key: str
     lam: float = 0.7
     pool: int = 50
+
+
+@dataclass(frozen=True)
+class DPP:
+    """``model.recommend(..., rerank=DPP(lookup, key, lam, pool))``: re-rank each impression's ``pool`` most relevant candidates
+    by greedy DPP MAP inference over the unit vectors ``lookup`` (a DeviceLookup) holds under ``key``.  ``pool`` must lie in
+    [top_n, 64]."""
+    lookup: DeviceLookup
+    key: str
+    lam: float = 0.7
+    pool: int = 50
+
+
+DPP_EPS = 1e-4  # the clamp of a conditional variance (ebn_dpp_rerank_f32)
 
 
 def check_lam(lam) -> float:
@@ -58,9 +91,7 @@ def _is_vector_key(lookup_dict, key: str) -> bool:
     return first is None or np.ndim(first[key]) == 1
 
 
-def mmr_select(unit, pool_rows, pool_rel, k: int, lam: float, flags, want_obj: bool = False):
-    """One ebn_mmr_rerank_f32 call on device tensors: unit [n_rows, D] float32, pool_rows [U, P] int32, pool_rel [U, P] float32
-    -> (sel [U, k] int32 pool indices, -1 in empty slots; obj [U, k] float32 or None).  ``flags`` [2] int32 accumulates."""
+def _pool_select(entry: str, unit, pool_rows, pool_rel, k: int, lam: float, flags, want_obj: bool):
     import torch
 
     from ebrec import _hip
@@ -69,18 +100,34 @@ def mmr_select(unit, pool_rows, pool_rel, k: int, lam: float, flags, want_obj: b
     sel = torch.empty(U, k, dtype=torch.int32, device=pool_rows.device)
     obj = torch.empty(U, k, dtype=torch.float32, device=pool_rows.device) if want_obj else None
     with torch.cuda.device(pool_rows.device):
-        _hip.call("ebn_mmr_rerank_f32", _hip.ptr(unit), unit.shape[0], unit.shape[1], _hip.ptr(pool_rows), _hip.ptr(pool_rel), P, k,
+        _hip.call(entry, _hip.ptr(unit), unit.shape[0], unit.shape[1], _hip.ptr(pool_rows), _hip.ptr(pool_rel), P, k,
                   float(lam), _hip.ptr(sel), _hip.ptr(obj), _hip.ptr(flags), U, _hip.stream_handle())
     return sel, obj
 
 
-def _host_select(vectors: np.ndarray, present: np.ndarray, rel: np.ndarray, k: int, lam: float) -> list:
-    """pool indices of one list, float64: vectors [P, D] as stored (normalised here, a zero row stays zero)"""
+def mmr_select(unit, pool_rows, pool_rel, k: int, lam: float, flags, want_obj: bool = False):
+    """One ebn_mmr_rerank_f32 call on device tensors: unit [n_rows, D] float32, pool_rows [U, P] int32, pool_rel [U, P] float32
+    -> (sel [U, k] int32 pool indices, -1 in empty slots; obj [U, k] float32 or None).  ``flags`` [2] int32 accumulates."""
+    return _pool_select("ebn_mmr_rerank_f32", unit, pool_rows, pool_rel, k, lam, flags, want_obj)
+
+
+def dpp_select(unit, pool_rows, pool_rel, k: int, lam: float, flags, want_obj: bool = False):
+    """One ebn_dpp_rerank_f32 call on device tensors, with the operands and results of ``mmr_select``."""
+    return _pool_select("ebn_dpp_rerank_f32", unit, pool_rows, pool_rel, k, lam, flags, want_obj)
+
+
+def _unit_distances(vectors: np.ndarray) -> np.ndarray:
+    """float64 [P, P] distances of the vectors as stored (normalised here, a zero row stays zero; a NaN dot product gives 0)"""
     norm = np.sqrt((vectors * vectors).sum(1, keepdims=True))
     unit = vectors / np.where(norm == 0, 1.0, norm)
     with np.errstate(invalid="ignore"):
         dist = np.clip(1.0 - unit @ unit.T, 0.0, 2.0)
-    dist = np.where(np.isnan(dist), 0.0, dist)
+    return np.where(np.isnan(dist), 0.0, dist)
+
+
+def _host_select(vectors: np.ndarray, present: np.ndarray, rel: np.ndarray, k: int, lam: float) -> list:
+    """pool indices of one list, float64: vectors [P, D] as stored (normalised here, a zero row stays zero)"""
+    dist = _unit_distances(vectors)
     left = present.copy()
     mind = np.full(len(rel), np.inf)
     picks = []
@@ -96,6 +143,28 @@ def _host_select(vectors: np.ndarray, present: np.ndarray, rel: np.ndarray, k: i
     return picks
 
 
+def _host_dpp_select(vectors: np.ndarray, present: np.ndarray, rel: np.ndarray, k: int, lam: float) -> list:
+    """pool indices of one list, float64, by the DPP recurrence of the module docstring: vectors [P, D] as stored"""
+    S = 1.0 - 0.5 * _unit_distances(vectors)
+    P = len(rel)
+    left = present.copy()
+    d2 = np.diag(S).copy()
+    chol = np.zeros((P, k))
+    picks = []
+    for t in range(k):
+        if not left.any():
+            break
+        obj = lam * np.where(left, rel, 0.0) + (1.0 - lam) * np.log(np.maximum(d2, DPP_EPS))
+        best = int(np.argmax(np.where(left, obj, -np.inf)))  # the first of equal objectives: the smaller pool index
+        picks.append(best)
+        left[best] = False
+        if d2[best] > DPP_EPS:  # else a degenerate pick: slot t stays zero
+            e = (S[best] - chol[:, :t] @ chol[best, :t]) / np.sqrt(d2[best])
+            chol[:, t] = e
+            d2 = d2 - e * e
+    return picks
+
+
 def mmr_rerank(ids, scores, lookup_dict, lookup_key: str, top_n: int, lam: float = 0.7, return_scores: bool = False, fill_id=-1):
     """ids [n, P] with their scores [n, P] -> ids [n, top_n]: the MMR order of each pool (module docstring), lists left shorter
     than ``top_n`` padded with ``fill_id``.  An id that is no key of ``lookup_dict`` and an entry whose score is not finite are
@@ -103,6 +172,19 @@ def mmr_rerank(ids, scores, lookup_dict, lookup_key: str, top_n: int, lam: float
     which is NOT monotone: a later pick may carry a higher score than an earlier one's successor would have.
     ValueError: ``lam`` outside [0, 1], P > 64, ``top_n`` outside [1, 64], ``lookup_key`` not a vector key, and, on the device
     path, a vector width that is no multiple of 4."""
+    return _rerank_by_vectors(mmr_select, _host_select, ids, scores, lookup_dict, lookup_key, top_n, lam, return_scores, fill_id)
+
+
+def dpp_rerank(ids, scores, lookup_dict, lookup_key: str, top_n: int, lam: float = 0.7, return_scores: bool = False, fill_id=-1):
+    """ids [n, P] with their scores [n, P] -> ids [n, top_n]: the greedy DPP order of each pool (module docstring), with the
+    arguments, absent entries, padding, ``return_scores`` (the given score of each kept entry, in selection order: NOT monotone)
+    and ValueErrors of ``mmr_rerank``."""
+    return _rerank_by_vectors(dpp_select, _host_dpp_select, ids, scores, lookup_dict, lookup_key, top_n, lam, return_scores, fill_id)
+
+
+def _rerank_by_vectors(device_select, host_select, ids, scores, lookup_dict, lookup_key, top_n, lam, return_scores, fill_id):
+    """the body of ``mmr_rerank`` and ``dpp_rerank``: the checks, the two paths (``device_select``: mmr_select or dpp_select,
+    ``host_select``: their float64 twins) and the padding"""
     lam = check_lam(lam)
     ids = np.asarray(ids)
     scores = np.asarray(scores)
@@ -132,7 +214,7 @@ def mmr_rerank(ids, scores, lookup_dict, lookup_key: str, top_n: int, lam: float
         rows = torch.from_numpy(lookup_dict.rows_of(ids).reshape(n, P)).to(unit.device)
         rel = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(unit.device)
         flags = torch.zeros(2, dtype=torch.int32, device=unit.device)
-        sel = mmr_select(unit, rows, rel, top_n, lam, flags)[0].cpu().numpy().astype(np.int64)
+        sel = device_select(unit, rows, rel, top_n, lam, flags)[0].cpu().numpy().astype(np.int64)
     else:
         sel = np.full((n, top_n), -1, np.int64)
         rel64 = scores.astype(np.float64)
@@ -145,7 +227,7 @@ def mmr_rerank(ids, scores, lookup_dict, lookup_key: str, top_n: int, lam: float
             vectors = np.zeros((P, D))
             for i in np.flatnonzero(present):
                 vectors[i] = lookup_dict[keys[i]][lookup_key]
-            picks = _host_select(vectors, present, rel64[r], top_n, lam)
+            picks = host_select(vectors, present, rel64[r], top_n, lam)
             sel[r, :len(picks)] = picks
     kept = np.maximum(sel, 0)
     out = np.where(sel >= 0, np.take_along_axis(ids, kept, 1), fill)

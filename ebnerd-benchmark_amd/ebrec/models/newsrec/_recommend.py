@@ -25,6 +25,8 @@ launch is ``ebn_npa_topk_score_f32`` (``npa_topk`` below, ``NPAModel.recommend_p
 ``rerank=MMR(lookup, key, lam, pool)`` (ebrec/evaluation/rerank.py) diversifies the lists: the same launch keeps each user's best
 ``pool``, their positions are mapped to rows of the lookup's unit table on the device, and ``ebn_mmr_rerank_f32`` picks ``top_n`` of
 them greedily by lam * score + (1 - lam) * (distance to the nearest item already picked).
+``rerank=DPP(lookup, key, lam, pool)`` takes the same path into ``ebn_dpp_rerank_f32``: greedy DPP MAP inference, each pick by
+lam * score + (1 - lam) * log(conditional variance of the item given the items already picked).
 ``rerank=Calibrated(lookup, key, lam, pool, alpha, target, history_weights)`` calibrates them instead: the pool is formed the same
 way, ``ebn_label_target_f32`` turns the batch's history rows (mapped to the lookup's rows through one host-built int32 map) into
 each user's target label distribution, and ``ebn_calibrated_rerank_f32`` picks ``top_n`` greedily by
@@ -57,8 +59,8 @@ import torch
 from ebrec import _hip
 from ebrec.evaluation.freshness import Freshness
 from ebrec.evaluation.rerank import (
-    MAX_HISTORY, MAX_LABELS, MAX_POOL, MMR, Calibrated, calibrated_select, check_alpha, check_history_weights, check_lam,
-    given_target, label_target, mmr_select,
+    DPP, MAX_HISTORY, MAX_LABELS, MAX_POOL, MMR, Calibrated, calibrated_select, check_alpha, check_history_weights, check_lam,
+    dpp_select, given_target, label_target, mmr_select,
 )
 
 MAX_TOP_N, MAX_EXCLUDE = 64, 256  # limits of ebn_topk_score_f32 (include/ebnerd_hip.h)
@@ -96,8 +98,9 @@ def _check(model, loader, top_n, scores):
 def _check_rerank(rerank, top_n, cand_ids):
     """Host side of ``rerank=``: -> (pool, lookup rows [M] int32 of the candidates).  Everything that can be wrong with the
     arguments is found here, before the device works."""
-    if not isinstance(rerank, (MMR, Calibrated)):
-        raise ValueError(f"rerank must be None or an MMR(lookup, key, lam, pool) or a Calibrated(lookup, key, ...), got {type(rerank).__name__}")
+    if not isinstance(rerank, (MMR, DPP, Calibrated)):
+        raise ValueError("rerank must be None or an MMR(lookup, key, lam, pool), a DPP(lookup, key, lam, pool) or a Calibrated(lookup, key, ...), "
+                         f"got {type(rerank).__name__}")
     check_lam(rerank.lam)
     pool = int(rerank.pool)
     if not top_n <= pool <= MAX_POOL:
@@ -105,16 +108,17 @@ def _check_rerank(rerank, top_n, cand_ids):
     lookup, key = rerank.lookup, rerank.key
     if isinstance(rerank, Calibrated):
         return min(pool, len(cand_ids)), _check_calibrated(rerank, cand_ids)
+    name = type(rerank).__name__  # MMR or DPP: one contract
     if not (hasattr(lookup, "holds") and lookup.holds(key) and key in lookup.vector_keys):
-        raise ValueError(f"MMR needs a DeviceLookup that holds '{key}' as a vector key")
+        raise ValueError(f"{name} needs a DeviceLookup that holds '{key}' as a vector key")
     rows = lookup.rows_of(cand_ids)
     if (rows < 0).any():
         missing = list(dict.fromkeys(np.asarray(cand_ids)[rows < 0].tolist()))
         more = f" and {len(missing) - 5} more" if len(missing) > 5 else ""
-        raise ValueError(f"candidate ids without a '{key}' vector in the MMR lookup: {missing[:5]}{more}")
+        raise ValueError(f"candidate ids without a '{key}' vector in the {name} lookup: {missing[:5]}{more}")
     D = lookup.host_table(key).shape[1]
     if D == 0 or D % 4:
-        raise ValueError(f"MMR needs a vector width that is a positive multiple of 4, '{key}' has {D}")
+        raise ValueError(f"{name} needs a vector width that is a positive multiple of 4, '{key}' has {D}")
     return min(pool, len(rows)), rows
 
 
@@ -364,6 +368,9 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     (``pool`` in [top_n, 64], clamped to the number of candidates; every candidate id must have a ``key`` vector in ``lookup``)
     with the score chosen by ``scores`` as the relevance; ``lam = 1`` gives the plain lists.  The returned scores are then still
     the MODEL's score of each kept item, in selection order: they are NOT monotone along a list.
+    ``rerank=DPP(lookup, key, lam=0.7, pool=50)``: the same pool, lookup and scores, each list in greedy DPP order
+    (ebrec/evaluation/rerank.py): lam * score + (1 - lam) * log(conditional variance given the items already picked), which
+    penalises an item spanned by several earlier picks even when it is close to none of them; ``lam = 1`` gives the plain lists.
     ``rerank=Calibrated(lookup, key, lam=0.7, pool=50, alpha=0.01, target="history", history_weights=None)``: each list is the
     greedy calibrated order of the same pool (ebrec/evaluation/rerank.py): lam * score - (1 - lam) * KL(target || list) over the
     labels ``lookup`` holds under the label key ``key``.  The target is the label distribution of the impression's own history --
@@ -395,7 +402,7 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     calibrated = isinstance(rerank, Calibrated)
     from_history = calibrated and isinstance(rerank.target, str)
     if rerank is not None:
-        unit = rerank.lookup.device_table(rerank.key).to(device)  # MMR: the unit rows; Calibrated: the label table
+        unit = rerank.lookup.device_table(rerank.key).to(device)  # MMR, DPP: the unit rows; Calibrated: the label table
         row_of_pos = torch.from_numpy(lookup_rows).to(device)  # candidate position -> row of the lookup's table
     if from_history:
         lookup_row_of_news = torch.from_numpy(_history_row_map(index, rerank.lookup, news_all.shape[0])).to(device)
@@ -420,7 +427,8 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
         pp, ps = launch(u, ex, pool, wd)
         pool_rows = torch.where(pp >= 0, row_of_pos[pp.clamp(min=0).long()], pp).contiguous()
         if not calibrated:
-            sel, _ = mmr_select(unit, pool_rows, ps, top_n, rerank.lam, flags)
+            select = dpp_select if isinstance(rerank, DPP) else mmr_select
+            sel, _ = select(unit, pool_rows, ps, top_n, rerank.lam, flags)
         else:
             if from_history:  # history rows of the catalogue -> rows of the label table (outside the catalogue: the padding)
                 inside = (hh >= 0) & (hh < lookup_row_of_news.shape[0])

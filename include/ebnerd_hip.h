@@ -1167,6 +1167,32 @@ int ebn_npa_target_rank_f32(const float* users, const float* Q, const float* Ua_
 int ebn_mmr_rerank_f32(const float* unit, int64_t n_rows, int32_t D, const int32_t* pool_rows, const float* pool_rel, int32_t P,
                        int32_t k, float lam, int32_t* out_sel, float* out_obj, int32_t* flags, int64_t U, ebn_stream_t stream);
 
+/* ---- DPP re-ranking of a relevance pool (greedy MAP inference of a determinantal point process, Chen, Zhang, Zhou, NeurIPS 2018:
+ * where MMR looks at a pick's NEAREST earlier pick, DPP scores the list jointly through log det of its similarity matrix) ----------
+ * The arguments, the pool, ABSENT entries, the flags, the limits and the error codes are those of ebn_mmr_rerank_f32, and so is
+ * d(i, j) = fminf(fmaxf(1 - u_i . u_j, 0), 2), the dot product in exact fp32 (one MFMA fma chain over D in a fixed order); a NaN dot
+ * product between two present entries -- an entry with itself included, the diagonal is used here -- gives d = 0 and sets flags[1].
+ * An absent entry's row is never turned into an address.
+ * Similarity S(i, j) = 1 - d(i, j) / 2: (1 + cos) / 2 for unit rows, positive semi-definite, in [0, 1], monotone in the cosine,
+ * the diagonal AS COMPUTED (1 up to rounding for a unit row, 1/2 for a zero row).  State per entry: d2_i, the conditional variance
+ * of i given the picks, initially S(i, i), and a Cholesky row c_i[0..t).  EPS = 1e-4f.
+ * Round t = 0, 1, ... picks, among the present entries not yet picked, the largest
+ *   obj_i = lam * rel_i + (1 - lam) * logf(fmaxf(d2_i, EPS))
+ * (lam * rel_i is the marginal gain of lam * sum rel + (1 - lam) * log det S_Y).  Larger obj first, equal obj to the smaller pool
+ * index.  After picking j: if d2_j <= EPS the pick is degenerate (already spanned by the picks) and nothing is updated but
+ * c_i[t] = 0; otherwise, for every present unpicked i,
+ *   e_i = (S(j, i) - sum_{s<t} c_j[s] c_i[s]) / sqrtf(d2_j),   c_i[t] = e_i,   d2_i -= e_i * e_i,
+ * the sum over s ascending in ONE fma chain.  The rounds end after k picks or when nothing is left.  A pool whose rank is below k
+ * still gives full-length lists: spanned entries are clamped at EPS, not dropped, and then order by relevance.  lam = 1 gives the
+ * relevance order of the pool (which need not arrive sorted) with out_obj = rel.  out_sel [U, k]: the pool INDEX of each pick, -1
+ * in the empty trailing slots; out_obj [U, k] (may be NULL): its objective, -inf in empty slots.  flags [2] is only ever SET.
+ * Limits: 1 <= P <= 64, 1 <= k <= 64 (k > P is legal: the lists come back short), D % 4 == 0, 4 <= D <= 8192 (EBN_ERR_UNSUPPORTED);
+ * lam outside [0, 1] or NaN: EBN_ERR_BAD_ARG; unit 16-byte aligned (EBN_ERR_ALIGN).  U == 0: nothing to do.  A failing call writes
+ * nothing.  One workgroup per user (two users when P <= 32), one wave of it running the rounds with the Cholesky rows in LDS, no
+ * atomics: a user's output bits depend neither on U nor on the users that share its launch, and two runs give the same bits.   */
+int ebn_dpp_rerank_f32(const float* unit, int64_t n_rows, int32_t D, const int32_t* pool_rows, const float* pool_rel, int32_t P,
+                       int32_t k, float lam, int32_t* out_sel, float* out_obj, int32_t* flags, int64_t U, ebn_stream_t stream);
+
 /* ---- calibrated re-ranking of a relevance pool (Steck, RecSys 2018: the greedy list whose label distribution stays close, in KL
  * divergence, to a target distribution -- what Distribution, beyond_accuracy.py:158-209, reports over category / sentiment_label /
  * topics in examples/beyond_accuracy/make_beyond_accuracy.ipynb) -----------------------------------------------------------------
