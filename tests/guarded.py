@@ -147,10 +147,11 @@ class Handle:
                 raise AssertionError(f"{what}: {int(bad.sum())} outputs were never written; first: {self._where(i)}")
 
 
-def _alloc(rows, width, ld, dtype, device, offset, bits):
+def _alloc(rows, width, ld, dtype, device, offset, bits, guard=None):
     assert dtype in _DTYPES, dtype
     assert ld >= width and offset in (0, 1, 2, 3)
-    g = guard_len(ld)
+    g = guard_len(ld) if guard is None else int(guard)
+    assert g >= 4096 and g % 4 == 0, g
     buf = torch.empty(g + 8 + rows * ld + g, dtype=dtype, device=device)
     assert buf.data_ptr() % 4 == 0
     start = g + (-(buf.data_ptr() // 4 + g)) % 4 + offset  # 16-byte aligned, then the deliberate misalignment
@@ -158,23 +159,24 @@ def _alloc(rows, width, ld, dtype, device, offset, bits):
     return buf, start
 
 
-def guard_in(x, ld=None, fill=float("nan"), device="cuda", offset=0):
+def guard_in(x, ld=None, fill=float("nan"), device="cuda", offset=0, guard=None):
     """x (numpy / tensor, 1-D or 2-D; more dimensions: the leading ones are flattened into rows) -> (view, handle).  The view has
     x's values at row stride `ld` (default: the width), a 16-byte aligned data_ptr() (+ `offset` floats for the deliberately
-    misaligned cases); guards and padding columns hold `fill`."""
+    misaligned cases); guards and padding columns hold `fill`.  `guard`: elements per side instead of guard_len(ld), for the long
+    flat operands of element-wise kernels (millions of elements in one row: nothing there strides by ld, and 256 * ld is GBs)."""
     x = torch.as_tensor(np.array(x))  # a copy: read-only reference arrays are welcome
     dtype = torch.int32 if not x.dtype.is_floating_point else torch.float32
     shape = tuple(x.shape) if x.dim() <= 2 else (int(np.prod(x.shape[:-1])), x.shape[-1])
     rows, width = (1, shape[0]) if len(shape) == 1 else shape
     ld = width if ld is None else int(ld)
-    buf, start = _alloc(rows, width, ld, dtype, device, offset, _fill_bits(fill, dtype) & 0xFFFFFFFF)
+    buf, start = _alloc(rows, width, ld, dtype, device, offset, _fill_bits(fill, dtype) & 0xFFFFFFFF, guard)
     buf[start:start + rows * ld].view(rows, ld)[:, :width].copy_(x.to(dtype).reshape(rows, width))
     h = Handle(buf, start, rows, width, ld, shape, is_out=False)
     assert h.view.data_ptr() % 16 == 4 * offset
     return h.view, h
 
 
-def guard_out(shape, ld=None, dtype=torch.float32, device="cuda", offset=0):
+def guard_out(shape, ld=None, dtype=torch.float32, device="cuda", offset=0, guard=None):
     """-> (view, handle) of an output of `shape` (1-D or 2-D) at row stride `ld`: canaries around and between the rows, the
     payload pre-filled (NaN pattern / second canary) so that handle.check() can tell an output that was never written."""
     shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
@@ -182,7 +184,7 @@ def guard_out(shape, ld=None, dtype=torch.float32, device="cuda", offset=0):
         shape = (int(np.prod(shape[:-1])), shape[-1])
     rows, width = (1, shape[0]) if len(shape) == 1 else shape
     ld = width if ld is None else int(ld)
-    buf, start = _alloc(rows, width, ld, dtype, device, offset, CANARY)
+    buf, start = _alloc(rows, width, ld, dtype, device, offset, CANARY, guard)
     pre = PREFILL_I32 if dtype == torch.int32 else PREFILL_F32
     _bits(buf)[start:start + rows * ld].view(rows, ld)[:, :width].fill_(pre)
     h = Handle(buf, start, rows, width, ld, shape, is_out=True)
