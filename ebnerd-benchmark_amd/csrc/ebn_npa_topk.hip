@@ -23,6 +23,16 @@
 // A pair's score bits depend only on the user's two rows and the catalogue row's data: every fma chain, the in-lane reduction order
 // and the (commutative) cross-half add are the same whatever the candidate's position, U, M or n_splits.  Lists are bit-identical for
 // every n_splits and from run to run.  The score is NOT bit-equal to ebn_pap_indexed_f32's, which pools first and dots second.
+//
+// Windowed form (ebn_npa_topk_score_window_f32, the WINDOWED instantiations): user u may only receive the candidate positions of
+// window[u] = [lo, hi), clamped to [0, M).  A lane holds ONE user for the whole walk, so the user's clamped range sits in two
+// registers (npa_rank_kernel<LT, true, false>'s arrangement; no per-row LDS table as in ebn_topk.hip).  A wave reduces its 32 ranges
+// to their union [vlo, vhi) over the non-empty ones and their intersection [ilo, ihi); the workgroup's union [wlo, whi) goes through
+// 8 ints of LDS behind the list plan and picks the steps the workgroup walks, dealt evenly over the n_splits ranges of ITS OWN step
+// span.  A wave whose union misses a visited step stages its share of the slabs and takes the barriers -- no MFMA, no expf pass, no
+// selection.  A score is offered only when its position also lies in the lane's window (one unsigned compare; a step inside the
+// wave's intersection takes the plain compare), so nothing outside a window reaches the queue, the NaN flag or the lists.  The
+// score statements are the plain form's: the same bits for the same (user rows, catalogue row) pair.
 #include "ebn_topk_list.h"
 
 namespace {
@@ -40,10 +50,13 @@ struct NpaTopkArgs : TopkList {
   const int32_t* cand_rows;
   int64_t M, n_rows;
   int32_t L, F, A, steps_per_split;
+  const int32_t* window;  // [U, 2] (lo, hi) candidate positions; the WINDOWED instantiations only
 };
 
-// LT: row tiles of one candidate (1: L <= 32, 2: L <= 64)
-template <int LT>
+constexpr int NT_WINDOW_LDS_BYTES = 8 * 4;  // (lo, hi) of the four waves' unions behind the plan of ebn_topk_list.h
+
+// LT: row tiles of one candidate (1: L <= 32, 2: L <= 64).  dynamic LDS layout: ebn_topk_list.h (WINDOWED: + wave unions[8])
+template <int LT, bool WINDOWED>
 __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) {
   constexpr int CPS = NT_ROW_TILES / LT;  // candidates of a step
   constexpr int LP = 32 * LT;             // padded L
@@ -84,9 +97,68 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
   bool saw_nan = false;
 
   const int64_t n_steps = (a.M + CPS - 1) / CPS;
-  const int64_t t_beg = static_cast<int64_t>(split) * a.steps_per_split;
+  int64_t t_beg = static_cast<int64_t>(split) * a.steps_per_split;
   int64_t t_end = t_beg + a.steps_per_split;
   t_end = t_end < n_steps ? t_end : n_steps;
+
+  // WINDOWED: this lane's user (column il of the wave's tile) and its clamped range; a column past the last user repeats the last
+  // user, window included; an empty range is [0, 0): no position passes
+  int lo = 0, hi = 0;
+  int wlo = 0, whi = 0, vlo = 0, vhi = 0, ilo = 0, ihi = 0;
+  if constexpr (WINDOWED) {
+    const int64_t ul = u0 + wave * 32 + il;
+    const bool live = ul < a.U;
+    const int64_t uc = live ? ul : a.U - 1;
+    lo = a.window[2 * uc];
+    hi = a.window[2 * uc + 1];
+    lo = lo > 0 ? lo : 0;
+    hi = static_cast<int64_t>(hi) < a.M ? hi : static_cast<int>(a.M);  // M <= INT32_MAX
+    if (lo >= hi) lo = hi = 0;
+    // the union of this wave [vlo, vhi) over the non-empty windows of its users below U, their intersection [ilo, ihi); the union
+    // of the workgroup [wlo, whi) through LDS.  All of them are wave-uniform.
+    int xlo = INT32_MAX, xhi = 0, nlo = 0, nhi = INT32_MAX;
+    if (live) {
+      if (lo < hi) {
+        xlo = lo;
+        xhi = hi;
+      }
+      nlo = lo;
+      nhi = hi;
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {  // both lane halves hold the same 32 users
+      const int o0 = __shfl_xor(xlo, off, 64), o1 = __shfl_xor(xhi, off, 64), o2 = __shfl_xor(nlo, off, 64), o3 = __shfl_xor(nhi, off, 64);
+      xlo = o0 < xlo ? o0 : xlo;
+      xhi = o1 > xhi ? o1 : xhi;
+      nlo = o2 > nlo ? o2 : nlo;
+      nhi = o3 < nhi ? o3 : nhi;
+    }
+    vlo = __builtin_amdgcn_readfirstlane(xlo);
+    vhi = __builtin_amdgcn_readfirstlane(xhi);
+    ilo = __builtin_amdgcn_readfirstlane(nlo);
+    ihi = __builtin_amdgcn_readfirstlane(nhi);
+    volatile int* wun = lds.lps + TK_BM * k;  // the end of the plan: topk_lds_bytes(k)
+    if (lane == 0) {
+      wun[2 * wave] = vlo;
+      wun[2 * wave + 1] = vhi;
+    }
+    __syncthreads();
+    wlo = INT32_MAX;
+    whi = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int l = wun[2 * w], h = wun[2 * w + 1];
+      wlo = l < wlo ? l : wlo;
+      whi = h > whi ? h : whi;
+    }
+    wlo = __builtin_amdgcn_readfirstlane(wlo);
+    whi = __builtin_amdgcn_readfirstlane(whi);
+    // the steps that meet the union (none: wlo = INT32_MAX, whi = 0), dealt evenly over the splits
+    const int64_t w_beg = wlo / CPS, w_end = wlo < whi ? (static_cast<int64_t>(whi) + CPS - 1) / CPS : w_beg;
+    const int64_t w_n = w_end - w_beg;
+    t_beg = w_beg + w_n * split / a.n_splits;
+    t_end = w_beg + w_n * (split + 1) / a.n_splits;
+  }
 
   for (int64_t t = t_beg; t < t_end; ++t) {
     const int64_t n0 = t * CPS;
@@ -98,7 +170,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
         const int64_t r = a.cand_rows != nullptr ? static_cast<int64_t>(a.cand_rows[c]) : c;
         if (r < 0 || r >= a.n_rows) {
           row = -1;  // never turned into an address
-          a.flags[0] = 1;
+          if (!WINDOWED || (c >= wlo && c < whi)) a.flags[0] = 1;  // a visited step also has positions outside the union
         } else {
           row = static_cast<int>(r);
         }
@@ -117,6 +189,9 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
       pa[i] = a.Ua + tok * A + kq4;
       pv[i] = a.Vd + tok * F + kq4;
     }
+
+    // WINDOWED: a wave none of whose users' windows meets the step fills the operand images and takes the barriers, nothing else
+    const bool wave_on = !WINDOWED || (n0 < vhi && n0 + CPS > vlo);
 
     // acc[j][r] = sum_k tokens[32 j + row(r, kl)][k] * users[32 wave + il][k]: tokens through ptok, this workgroup's users through pusr
     auto gemm = [&](const float* const(&ptok)[2], const float* const(&pusr)[2], const int K, f32x16(&acc)[NT_ROW_TILES]) {
@@ -174,12 +249,12 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
       __syncthreads();
       for (int kt = 0; kt < nk; kt += 2) {
         if (kt + 1 < nk) fetch(kt + 1);
-        mma(0);
+        if (wave_on) mma(0);
         if (kt + 1 < nk) store(1);
         __syncthreads();
         if (kt + 1 < nk) {
           if (kt + 2 < nk) fetch(kt + 2);
-          mma(1);
+          if (wave_on) mma(1);
           if (kt + 2 < nk) store(0);
           __syncthreads();
         }
@@ -193,6 +268,10 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
     float den[CPS];
 #pragma unroll
     for (int c = 0; c < CPS; ++c) {
+      if (!wave_on) {  // wave-uniform; never true in the plain form
+        den[c] = 1.f;
+        continue;
+      }
       float m = -INFINITY;
 #pragma unroll
       for (int lt = 0; lt < LT; ++lt)
@@ -219,6 +298,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
     // ---- phase 2: dots, and the score (both lane halves end with the same bits: the cross-half add is commutative)
     f32x16 dv[NT_ROW_TILES];
     gemm(pv, pu, F, dv);
+    if (!wave_on) continue;  // wave-uniform; the barriers of the step are all behind it, the drain has none
     auto score = [&](const int c) {
       float num = 0.f;
 #pragma unroll
@@ -234,8 +314,13 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
     const int rl = wave * 32 + il;
     const float th = thr[rl];
     int cnt = 0;
+    // WINDOWED: the position must lie in the user's window as well -- unless the step is inside every window of this wave's users.
+    // lo <= p < hi as ONE unsigned compare: (p - lo) < (hi - lo); 0 <= lo <= hi <= M and p < 2^31, nothing wraps
+    const bool gated = WINDOWED && !(n0 >= ilo && n0 + CPS <= ihi);
+    const unsigned wd = gated ? static_cast<unsigned>(hi - lo) : UINT32_MAX;
+    const int d0 = static_cast<int>(n0) - (gated ? lo : 0);
     auto offer = [&](const float s, const int c) {
-      const bool pass = !(s < th);
+      const bool pass = !(s < th) && (!WINDOWED || static_cast<unsigned>(d0 + c) < wd);
       const unsigned long long m = __ballot(pass);
       if (pass) {
         const int slot = cnt + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
@@ -269,16 +354,17 @@ int npa_resolve_splits(int64_t U, int64_t M, int32_t L, int32_t n_splits) {
   return static_cast<int>(s < 1 ? 1 : s);
 }
 
-template <int LT>
+template <int LT, bool WINDOWED>
 int npa_launch(const NpaTopkArgs& a, int64_t user_tiles, int splits, hipStream_t s) {
+  constexpr int extra = WINDOWED ? NT_WINDOW_LDS_BYTES : 0;
   // above the 64 KB a kernel may use without asking (k > 44); set per call: the attribute belongs to the current device
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(npa_topk_kernel<LT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(topk_lds_bytes(TK_MAX_K))) != hipSuccess) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(npa_topk_kernel<LT, WINDOWED>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(topk_lds_bytes(TK_MAX_K)) + extra) != hipSuccess) {
     (void)hipGetLastError();
     return EBN_ERR_UNSUPPORTED;
   }
-  EBN_LAUNCH(npa_topk_kernel<LT>, dim3(static_cast<unsigned>(user_tiles), static_cast<unsigned>(splits)), dim3(TK_THREADS),
-             static_cast<size_t>(topk_lds_bytes(a.k)), s, a);
+  EBN_LAUNCH((npa_topk_kernel<LT, WINDOWED>), dim3(static_cast<unsigned>(user_tiles), static_cast<unsigned>(splits)), dim3(TK_THREADS),
+             static_cast<size_t>(topk_lds_bytes(a.k) + extra), s, a);
   EBN_CHECK_LAUNCH();
   return EBN_OK;
 }
@@ -295,10 +381,14 @@ extern "C" int ebn_npa_topk_auto_splits(int64_t n_users, int64_t n_cand, int32_t
   return static_cast<int>(s < 1 ? 1 : s);
 }
 
-extern "C" int ebn_npa_topk_score_f32(const float* users, const float* Q, const float* Ua_all, const float* Vd_all, int64_t n_rows,
-                                      const int32_t* cand_rows, int64_t M, const int32_t* exclude, int32_t X, int32_t k, int32_t mode,
-                                      int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace,
-                                      int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A, ebn_stream_t stream) {
+namespace {
+
+// both entry points: the checks, the plan and the launches; WINDOWED adds the window argument and 32 bytes of LDS
+template <bool WINDOWED>
+int npa_topk_score(const float* users, const float* Q, const float* Ua_all, const float* Vd_all, int64_t n_rows, const int32_t* cand_rows,
+                   int64_t M, const int32_t* window, const int32_t* exclude, int32_t X, int32_t k, int32_t mode, int32_t n_splits,
+                   int32_t* out_pos, float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, int32_t L,
+                   int32_t F, int32_t A, ebn_stream_t stream) {
   EBN_REQUIRE(ebn_dim_ok(U, M, n_rows) && L >= 0 && F >= 0 && A >= 0 && X >= 0 && n_splits >= 0 && workspace_bytes >= 0, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(mode == 0 || mode == 1, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(k >= 1 && k <= TK_MAX_K && X <= TK_MAX_X && L >= 1 && L <= NT_MAX_L, EBN_ERR_UNSUPPORTED);
@@ -306,6 +396,7 @@ extern "C" int ebn_npa_topk_score_f32(const float* users, const float* Q, const 
   EBN_REQUIRE(cand_rows != nullptr || M == n_rows, EBN_ERR_BAD_ARG);
   if (U == 0) return EBN_OK;
   EBN_REQUIRE(out_pos != nullptr && out_score != nullptr && flags != nullptr, EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(!WINDOWED || window != nullptr, EBN_ERR_BAD_ARG);
   hipStream_t s = ebn_stream(stream);
   if (M == 0) return topk_launch_fill_empty(out_pos, out_score, U, k, s);
   EBN_REQUIRE(users != nullptr && Q != nullptr && Ua_all != nullptr && Vd_all != nullptr && n_rows >= 1, EBN_ERR_BAD_ARG);
@@ -320,6 +411,7 @@ extern "C" int ebn_npa_topk_score_f32(const float* users, const float* Q, const 
   a.Ua = Ua_all;
   a.Vd = Vd_all;
   a.cand_rows = cand_rows;
+  a.window = window;
   a.exclude = exclude;
   a.out_pos = out_pos;
   a.out_score = out_score;
@@ -337,8 +429,27 @@ extern "C" int ebn_npa_topk_score_f32(const float* users, const float* Q, const 
   a.steps_per_split = static_cast<int32_t>(ebn_ceil_div(ebn_ceil_div(M, npa_cands_per_step(L)), splits));
   int rc = topk_bind_workspace(a, splits, workspace, workspace_bytes);
   if (rc != EBN_OK) return rc;
-  rc = L <= 32 ? npa_launch<1>(a, user_tiles, splits, s) : npa_launch<2>(a, user_tiles, splits, s);
+  rc = L <= 32 ? npa_launch<1, WINDOWED>(a, user_tiles, splits, s) : npa_launch<2, WINDOWED>(a, user_tiles, splits, s);
   if (rc != EBN_OK) return rc;
   if (splits > 1) return topk_launch_merge(a, s);
   return EBN_OK;
+}
+
+}  // namespace
+
+extern "C" int ebn_npa_topk_score_f32(const float* users, const float* Q, const float* Ua_all, const float* Vd_all, int64_t n_rows,
+                                      const int32_t* cand_rows, int64_t M, const int32_t* exclude, int32_t X, int32_t k, int32_t mode,
+                                      int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace,
+                                      int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A, ebn_stream_t stream) {
+  return npa_topk_score<false>(users, Q, Ua_all, Vd_all, n_rows, cand_rows, M, nullptr, exclude, X, k, mode, n_splits, out_pos, out_score,
+                               flags, workspace, workspace_bytes, U, L, F, A, stream);
+}
+
+extern "C" int ebn_npa_topk_score_window_f32(const float* users, const float* Q, const float* Ua_all, const float* Vd_all, int64_t n_rows,
+                                             const int32_t* cand_rows, int64_t M, const int32_t* window, const int32_t* exclude, int32_t X,
+                                             int32_t k, int32_t mode, int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags,
+                                             void* workspace, int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A,
+                                             ebn_stream_t stream) {
+  return npa_topk_score<true>(users, Q, Ua_all, Vd_all, n_rows, cand_rows, M, window, exclude, X, k, mode, n_splits, out_pos, out_score,
+                              flags, workspace, workspace_bytes, U, L, F, A, stream);
 }

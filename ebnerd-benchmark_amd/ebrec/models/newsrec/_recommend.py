@@ -20,7 +20,12 @@ and, where act(user . news) is not its score, a fourth that replaces the scoring
 with ``users`` the concatenated first results of ``_user_vectors_cached`` (whatever the model packs into a row) and the contract of
 ``ebn_topk_score_f32`` for everything else.  ``_recommend_cache`` then returns, in place of ``news_all``, any device tensor with one
 leading row per catalogue row.  NPA is the one such model: its news vector depends on the user, a row is ``user_vec | Qn`` and the
-launch is ``ebn_npa_topk_score_f32`` (``npa_topk`` below, ``NPAModel.recommend_pairwise``).
+launch is ``ebn_npa_topk_score_f32`` (``npa_topk`` below, ``NPAModel.recommend_pairwise``).  Such a model offers the windowed form of
+its launch (see ``window=`` below) as one more hook, passed to the body both entries share (``_recommend``):
+
+    _recommend_topk_window(cache, users, cand_rows, window, exclude, k, sigmoid, flags) -> (pos [U, k] int32, score [U, k] float32)
+
+NPA's is ``ebn_npa_topk_score_window_f32`` (``npa_topk_window`` below) behind ``NPAModel.recommend_pairwise_windowed``.
 
 ``rerank=MMR(lookup, key, lam, pool)`` (ebrec/evaluation/rerank.py) diversifies the lists: the same launch keeps each user's best
 ``pool``, their positions are mapped to rows of the lookup's unit table on the device, and ``ebn_mmr_rerank_f32`` picks ``top_n`` of
@@ -46,8 +51,8 @@ its counting form as a fifth hook, passed to the same body (``_rank_targets``):
 
     _rank_launch(cache, users, cand_rows, target_pos, window, exclude, sigmoid, flags) -> (rank [U], count [U], score [U])
 
-NPA's is ``ebn_npa_target_rank_f32`` (``npa_target_rank`` below) behind ``NPAModel.rank_targets_pairwise``; it takes windows, while
-NPA's windowed top-N lists do not exist yet.
+NPA's is ``ebn_npa_target_rank_f32`` (``npa_target_rank`` below) behind ``NPAModel.rank_targets_pairwise``; it takes windows, and the
+lists its windowed ranks refer to are those of ``NPAModel.recommend_pairwise_windowed``.
 """
 from __future__ import annotations
 
@@ -218,6 +223,29 @@ def npa_topk(users: torch.Tensor, Q: torch.Tensor, Ua_all: torch.Tensor, Vd_all:
     return pos, score
 
 
+def npa_topk_window(users: torch.Tensor, Q: torch.Tensor, Ua_all: torch.Tensor, Vd_all: torch.Tensor, cand_rows, window: torch.Tensor,
+                    exclude, k: int, sigmoid: bool, flags: torch.Tensor, n_splits: int = 0):
+    """One ebn_npa_topk_score_window_f32 call on device tensors: ``npa_topk`` with window [U, 2] int32, user u may only receive the
+    candidate positions window[u, 0] <= c < window[u, 1] -> (pos [U, k] int32, score [U, k] float32); ``flags`` accumulates.
+    Cheapest with the users sorted by window[:, 0]: a workgroup of 128 users skips the candidate steps none of their windows meets."""
+    U, F = users.shape
+    n_rows, L, A = Ua_all.shape
+    M = n_rows if cand_rows is None else cand_rows.shape[0]
+    X = 0 if exclude is None else exclude.shape[1]
+    if window.shape != (U, 2) or window.dtype != torch.int32 or not window.is_contiguous():
+        raise ValueError(f"window must be a contiguous [{U}, 2] int32 tensor, got {tuple(window.shape)} {window.dtype}")
+    pos = torch.empty(U, k, dtype=torch.int32, device=users.device)
+    score = torch.empty(U, k, dtype=torch.float32, device=users.device)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_npa_topk_auto_splits(U, M, L))
+    ws_bytes = int(lib.ebn_topk_workspace_bytes(U, k, max(splits, 1)))  # the partial lists are ebn_topk_score_f32's
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=users.device)
+    _hip.call("ebn_npa_topk_score_window_f32", _hip.ptr(users), _hip.ptr(Q), _hip.ptr(Ua_all), _hip.ptr(Vd_all), n_rows, _hip.ptr(cand_rows),
+              M, _hip.ptr(window), _hip.ptr(exclude), X, k, 1 if sigmoid else 0, splits, _hip.ptr(pos), _hip.ptr(score), _hip.ptr(flags),
+              _hip.ptr(ws), ws.numel(), U, L, F, A, _hip.stream_handle())
+    return pos, score
+
+
 def target_rank(users: torch.Tensor, news_all: torch.Tensor, cand_rows, target_pos: torch.Tensor, window, exclude, sigmoid: bool,
                 flags: torch.Tensor, n_splits: int = 0):
     """One ebn_target_rank_f32 call on device tensors: target_pos [U] int32 positions in the candidate list (< 0: none), window
@@ -381,8 +409,18 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     time.  The tie rule then reads: equal scores go to the OLDER article, then to the earlier position in ``candidate_ids``.  A
     window holding fewer than ``top_n`` candidates gives a list padded with ``fill_id``; ``rerank=`` works on top unchanged (its
     pool is the window's best, a history target is not touched by the window).  Not for models with a scoring launch of their
-    own (NPA)."""
+    own (NPA: ``NPAModel.recommend_pairwise_windowed``)."""
     _check_window(model, window)
+    return _recommend(model, loader, candidate_ids, top_n, exclude_history, return_scores, scores, fill_id, users_per_call, rerank, window)
+
+
+def _recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True, return_scores=False, scores="sigmoid", fill_id=-1,
+               users_per_call=65536, rerank=None, window=None, model_window_launch=None):
+    """The body of ``recommend``.  ``model_window_launch(cache, users, cand_rows, window, exclude, k, sigmoid, flags)`` -> (pos, score)
+    is the windowed form of the model's own scoring launch (``NPAModel._recommend_topk_window``), or None: ``topk_window`` over
+    act(user . news)."""
+    if window is not None and not isinstance(window, Freshness):
+        raise ValueError(f"window must be None or a Freshness(published, max_age, min_age), got {type(window).__name__}")
     _check(model, loader, top_n, scores)
     top_n = int(top_n)
     index = model._recommend_index(loader)
@@ -412,7 +450,9 @@ def recommend(model, loader, candidate_ids=None, top_n=10, exclude_history=True,
     need_his = exclude_history or from_history
     sigmoid = scores == "sigmoid"
     model_topk = getattr(model, "_recommend_topk", None)  # the scoring launch: the model's own, or act(user . news)
-    if window is not None:
+    if window is not None and model_window_launch is not None:
+        launch = lambda u, ex, k, w: model_window_launch(cache, u, cand_d, w, ex, k, sigmoid, flags)
+    elif window is not None:
         launch = lambda u, ex, k, w: topk_window(u, news_all, cand_d, w, ex, k, sigmoid, flags)
     elif model_topk is None:
         launch = lambda u, ex, k, w: topk(u, news_all, cand_d, ex, k, sigmoid, flags)

@@ -16,9 +16,12 @@ Inputs are ``(user_indexes (B,1), his_input_title (B,H,T), pred_input_title (B,C
   * ``recommend_pairwise(loader, candidate_ids, top_n=...)`` gives each impression's top-N of one shared candidate list from the
     same once-encoded catalogue: NPA has no per-article vector, so ``ebn_npa_topk_score_f32`` computes every (user, candidate)
     pair's logits and dots on the matrix cores, pools and selects in one launch (``_recommend.py``); ``recommend`` still raises;
+  * ``recommend_pairwise_windowed(loader, candidate_ids, window=Freshness(...), top_n=...)`` gives the same lists inside each
+    impression's freshness window (``ebn_npa_topk_score_window_f32``: a workgroup walks only the candidate steps its users'
+    windows meet); ``recommend_pairwise(..., window=...)`` still raises;
   * ``rank_targets_pairwise(loader, targets, candidate_ids, ...)`` is the accuracy side of those lists: the place of each clicked
     article among all candidates, from ``ebn_npa_target_rank_f32`` -- the same step with a count in place of the selection, also
-    inside ``window=Freshness(...)``; ``rank_targets`` still raises.
+    inside ``window=Freshness(...)``, where the lists are ``recommend_pairwise_windowed``'s; ``rank_targets`` still raises.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import torch
 
 from ._engine_npa import NPAEngine
 from ._keras_like import ModelBase
-from ._recommend import TargetRanks, _rank_targets, npa_target_rank, npa_topk, recommend
+from ._recommend import TargetRanks, _rank_targets, _recommend, npa_target_rank, npa_topk, npa_topk_window, recommend
 
 
 class NPAModel(ModelBase):
@@ -120,8 +123,24 @@ class NPAModel(ModelBase):
     def recommend_pairwise(self, loader, candidate_ids=None, **kwargs):
         """Each impression's top_n of one shared candidate list (``_recommend.recommend``: the same arguments, defaults, results and
         errors as the other models' ``recommend``), every (user, candidate) pair scored by personalised pooling from the
-        once-encoded catalogue."""
+        once-encoded catalogue.  ``window=`` raises here: the lists inside freshness windows are ``recommend_pairwise_windowed``'s."""
         return recommend(self, loader, candidate_ids, **kwargs)
+
+    def _recommend_topk_window(self, cache, users, cand_rows, window, exclude, k, sigmoid, flags):
+        """The windowed scoring launch of ``_recommend._recommend`` for rows ``user_vec | Qn``: ebn_npa_topk_score_window_f32."""
+        F = self._engine.F
+        return npa_topk_window(users[:, :F].contiguous(), users[:, F:].contiguous(), cache.Ua_all, cache.Vd_all, cand_rows, window, exclude,
+                               k, sigmoid, flags)
+
+    def recommend_pairwise_windowed(self, loader, candidate_ids=None, *, window, **kwargs):
+        """``recommend_pairwise`` inside freshness windows: the arguments, defaults, results and errors of the other models'
+        ``recommend(..., window=Freshness(...))``, ``rerank=`` included.  An impression at time t is only offered the candidates
+        published in [t - max_age, t - min_age]: the candidates are sorted by publish time, the users of a launch by the start of
+        their range, and ``ebn_npa_topk_score_window_f32`` lets a 128-user workgroup pool and score only the candidate steps its
+        users' ranges meet.  A pair's score has the bits ``recommend_pairwise`` gives it.  ``window`` is required."""
+        if window is None:
+            raise ValueError("recommend_pairwise_windowed needs window=Freshness(...); the lists without windows are recommend_pairwise's")
+        return _recommend(self, loader, candidate_ids, window=window, model_window_launch=self._recommend_topk_window, **kwargs)
 
     # -- the accuracy side of the same lists: ``rank_targets`` still raises, ``rank_targets_pairwise`` does the work ----------------
     def _rank_launch(self, cache, users, cand_rows, target_pos, window, exclude, sigmoid, flags):
@@ -135,9 +154,9 @@ class NPAModel(ModelBase):
         arguments, defaults, results and errors as the other models' ``rank_targets``, ``window=Freshness(...)`` included), every
         (user, candidate) pair scored by personalised pooling from the once-encoded catalogue and counted in the same launch
         (``ebn_npa_target_rank_f32``).  The rule: ``rank`` r <= k holds exactly when ``recommend_pairwise(loader, candidate_ids,
-        top_n=k, exclude_history=...)`` has the target at index r - 1, and ``score`` is that slot's score, bit for bit.  Windowed
-        top-N lists for NPA do not exist yet (``recommend_pairwise(..., window=...)`` raises), so under ``window=`` the ranks have
-        no list to be compared with: they follow the same rule inside each impression's window.  A catalogue above
+        top_n=k, exclude_history=...)`` has the target at index r - 1, and ``score`` is that slot's score, bit for bit.  Under
+        ``window=`` the list is ``recommend_pairwise_windowed``'s with the same window and the rule holds inside each impression's
+        window (windowed lists under the name ``recommend_pairwise`` do not exist yet: its ``window=`` raises).  A catalogue above
         ``catalogue_max_bytes`` raises, as it does for ``recommend_pairwise``."""
         return _rank_targets(self, loader, targets, candidate_ids, model_launch=self._rank_launch, **kwargs)
 

@@ -1114,6 +1114,29 @@ int ebn_npa_topk_score_f32(const float* users, const float* Q, const float* Ua_a
                            const int32_t* cand_rows, int64_t M, const int32_t* exclude, int32_t X, int32_t k, int32_t mode,
                            int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace,
                            int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A, ebn_stream_t stream);
+/* The same with a window of candidate positions per user: what ebn_topk_score_window_f32 is to ebn_topk_score_f32.  window [U, 2]
+ * int32 on the DEVICE, (lo_u, hi_u) = window[u]: user u may receive position c only when max(lo_u, 0) <= c < min(hi_u, M);
+ * lo_u >= hi_u after clamping gives an empty list (-1 / -inf).  window == NULL is EBN_ERR_BAD_ARG: the unwindowed call is
+ * ebn_npa_topk_score_f32.
+ * ebn_npa_topk_score_f32's inside a window: the operands and the pair score, the total order, exclude, cand_rows == NULL, duplicate
+ * rows, mode, padded tokens, the limits, the alignment and argument codes (all checked on the host before anything is launched: a
+ * failing call writes nothing), U == 0 (nothing to do), M == 0 (the outputs are filled as empty), the workspace
+ * (ebn_topk_workspace_bytes) and n_splits (0 = ebn_npa_topk_auto_splits(U, M, L); clamped to the catalogue's steps and to 64).  A
+ * score's bits are those ebn_npa_topk_score_f32 gives the same (user rows, catalogue row) pair: the same fma chains, in-lane
+ * reduction order, cross-half add and division; a list depends neither on n_splits, nor on the run, nor on which other users share
+ * the launch.
+ * ebn_topk_score_window_f32's: a 128-user workgroup visits only the candidate steps (4 candidates for L <= 32, 2 above) that meet the
+ * union of its users' windows -- its steps, not the catalogue's, are what n_splits divides -- so users sorted by lo cost in
+ * proportion to the window, not to M.  Hence the flags: flags[1] is set only by a NaN score of a pair inside that user's window -- a
+ * NaN outside it is never looked at.  flags[0] is set when a cand_rows entry outside [0, n_rows) lies in the window of at least one
+ * user, and is not set when no such entry lies in [min lo, max hi) over all users; for an entry in between -- inside that span but
+ * in no user's window -- EITHER value may come back: it is seen iff it lies between the lowest lo and the highest hi of one
+ * 128-user workgroup.                                                                                                              */
+int ebn_npa_topk_score_window_f32(const float* users, const float* Q, const float* Ua_all, const float* Vd_all, int64_t n_rows,
+                                  const int32_t* cand_rows, int64_t M, const int32_t* window, const int32_t* exclude, int32_t X,
+                                  int32_t k, int32_t mode, int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags,
+                                  void* workspace, int64_t workspace_bytes, int64_t U, int32_t L, int32_t F, int32_t A,
+                                  ebn_stream_t stream);
 
 /* ---- full-catalogue rank of one target candidate per user for NPA (the accuracy side of the same workflow for npa.py: where the
  * clicked article stands among all candidates NPA's top-N is drawn from) --------------------------------------------------------------
