@@ -3,7 +3,10 @@
 //   bias + dropout + residual + LayerNorm in the two orders the model uses, forward and backward;
 //   the fast additive attention core (FastSelfAttention without its three big Linear layers), forward and backward;
 //   bias + erf-gelu, forward and backward;  AttentionPooling after its first Linear (scalar bias, mask, 1e-8), forward and backward;
-//   the scoring head (concat-dot + sigmoid), forward and backward.
+//   the scoring head (concat-dot + sigmoid), forward and backward;
+//   for Fastformer_wu (reference models/fastformer/fastformer_wu.py): the embedding LayerNorm with one position row per token
+//   (forward; its backward is the mode-0 backward plus a column-sum finish over dX) and the class head with a stable softmax
+//   cross-entropy, forward and backward.
 //
 // Exact fp32, fixed summation orders, no float atomics: the same bits on every run.  Column sums (bias / gamma / beta / logit-weight
 // gradients) leave one partial per workgroup, each summed in a fixed order, and ebn_ff_colsum_finish_f32 adds the partials in ascending
@@ -305,6 +308,159 @@ __global__ __launch_bounds__(FF_THREADS) void ff_head_bwd_kernel(const float* __
     duser[n * D + k] = dz * W[k];
     dcand[n * D + k] = dz * W[D + k];
   }
+}
+
+// ---- Fastformer_wu (reference models/fastformer/fastformer_wu.py) -----------------------------------------------------------------
+// StandardFastformerEncoder's embedding LayerNorm: mode 0 of ff_ln_fwd_kernel with one position row PER TOKEN, row r reads
+// pos[r % T]; bias may be NULL.  z = x (+ bias) + pos[r % T],  y = drop(gamma * xhat + beta).  One wave per row, z parked in Y.
+__global__ __launch_bounds__(FF_THREADS) void ff_ln_pos_fwd_kernel(const float* __restrict__ X, const float* __restrict__ bias,
+                                                                   const float* __restrict__ pos, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ beta, float eps, FfDrop dr,
+                                                                   float* __restrict__ Y, float* __restrict__ xhat,
+                                                                   float* __restrict__ rstd, int64_t R, int T, int D) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * FF_WAVES + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int64_t off = r * D;
+  const float* prow = pos + (r % T) * D;
+  float s = 0.f;
+  for (int c = lane; c < D; c += 64) {
+    float z = X[off + c];
+    if (bias != nullptr) z += bias[c];
+    z += prow[c];
+    Y[off + c] = z;
+    s += z;
+  }
+  const float mean = ebn_wave_sum(s) / static_cast<float>(D);
+  float v = 0.f;
+  for (int c = lane; c < D; c += 64) {
+    const float d = Y[off + c] - mean;
+    v = fmaf(d, d, v);
+  }
+  const float rs = 1.0f / sqrtf(ebn_wave_sum(v) / static_cast<float>(D) + eps);
+  if (lane == 0 && rstd != nullptr) rstd[r] = rs;
+  for (int c = lane; c < D; c += 64) {
+    const float xh = (Y[off + c] - mean) * rs;
+    if (xhat != nullptr) xhat[off + c] = xh;
+    Y[off + c] = fmaf(xh, gamma[c], beta[c]) * ff_mult(dr, off + c);
+  }
+}
+
+// the class head: logits = X . W^T + b, a stable log-softmax per row and the row's cross-entropy term.  One wave per row; lane c
+// keeps class c's logit (C <= 64).  rowloss[n] = log(sum_c exp(l_c - m)) + m - l_y, or 0 and flag[0] = 1 for a target outside [0, C)
+__global__ __launch_bounds__(FF_THREADS) void ff_cls_fwd_kernel(const float* __restrict__ X, const float* __restrict__ W,
+                                                                const float* __restrict__ b, const int64_t* __restrict__ targets,
+                                                                float* __restrict__ logits, float* __restrict__ prob,
+                                                                float* __restrict__ rowloss, int32_t* __restrict__ flag, int64_t N,
+                                                                int D, int C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * FF_WAVES + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const float* x = X + n * D;
+  float mine = -INFINITY;
+  for (int c = 0; c < C; ++c) {
+    const float* w = W + static_cast<int64_t>(c) * D;
+    float p = 0.f;
+    for (int k = lane; k < D; k += 64) p = fmaf(x[k], w[k], p);
+    p = ebn_wave_sum(p) + b[c];
+    if (lane == c) mine = p;
+  }
+  const float m = ebn_wave_max(mine);
+  const float e = lane < C ? expf(mine - m) : 0.f;
+  const float s = ebn_wave_sum(e);
+  if (lane < C) {
+    logits[n * C + lane] = mine;
+    prob[n * C + lane] = e / s;
+  }
+  const int64_t y = targets[n];
+  const bool ok = y >= 0 && y < C;
+  const float ly = __shfl(mine, ok ? static_cast<int>(y) : 0, 64);
+  if (lane == 0) {
+    rowloss[n] = ok ? (logf(s) + m) - ly : 0.f;
+    if (!ok) flag[0] = 1;
+  }
+}
+
+// loss[0] = (sum_n rowloss[n]) / N: 256 chains of ascending n, combined by a fixed halving tree in LDS
+__global__ __launch_bounds__(FF_THREADS) void ff_cls_loss_kernel(const float* __restrict__ rowloss, float* __restrict__ loss,
+                                                                 int64_t N) {
+  __shared__ float sm[FF_THREADS];
+  float a = 0.f;
+  for (int64_t n = threadIdx.x; n < N; n += FF_THREADS) a += rowloss[n];
+  sm[threadIdx.x] = a;
+  __syncthreads();
+  for (int h = FF_THREADS / 2; h > 0; h >>= 1) {
+    if (static_cast<int>(threadIdx.x) < h) sm[threadIdx.x] += sm[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = N > 0 ? sm[0] / static_cast<float>(N) : 0.f;
+}
+
+constexpr int FF_CLS_MAX_C = 64;
+constexpr int FF_CLS_MAX_D = 1024;
+constexpr int FF_CLS_TILE = 32;        // rows whose dlogits a workgroup of the backward keeps in LDS at a time
+constexpr int FF_CLS_MAX_PARTS = 128;  // workgroups (= partials) of the backward
+
+// backward: workgroup g owns rows [g * rpb, (g + 1) * rpb) and walks them in tiles of 32: dlogits of the tile into LDS
+// (dloss / N * (p - onehot), nothing from a row whose target is out of range, + dscore), dX rows by the waves (c ascending), then
+// every thread adds the tile's rows in ascending order to the elements it owns of partials[g] = dW [C, D] | db [C]
+__global__ __launch_bounds__(FF_THREADS) void ff_cls_bwd_kernel(const float* __restrict__ X, const float* __restrict__ W,
+                                                                const float* __restrict__ prob, const int64_t* __restrict__ targets,
+                                                                const float* __restrict__ dloss, const float* __restrict__ dscore,
+                                                                float* __restrict__ dX, float* __restrict__ partials, int64_t N,
+                                                                int D, int C, int64_t rpb) {
+  __shared__ float sdl[FF_CLS_TILE * FF_CLS_MAX_C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * rpb;
+  const int64_t r1 = r0 + rpb < N ? r0 + rpb : N;
+  const float scale = (dloss != nullptr && N > 0) ? dloss[0] / static_cast<float>(N) : 0.f;
+  const int width = C * D + C;
+  float* out = partials + static_cast<int64_t>(blockIdx.x) * width;
+  for (int i = threadIdx.x; i < width; i += FF_THREADS) out[i] = 0.f;  // a thread only ever touches the elements it owns
+  for (int64_t t0 = r0; t0 < r1; t0 += FF_CLS_TILE) {
+    const int rows = static_cast<int>(r1 - t0 < FF_CLS_TILE ? r1 - t0 : FF_CLS_TILE);
+    __syncthreads();  // the previous tile's readers are done
+    for (int i = threadIdx.x; i < rows * C; i += FF_THREADS) {
+      const int r = i / C, c = i - r * C;
+      const int64_t n = t0 + r;
+      const int64_t y = targets[n];
+      float g = (y >= 0 && y < C) ? scale * (prob[n * C + c] - (c == y ? 1.0f : 0.0f)) : 0.f;
+      if (dscore != nullptr) g += dscore[n * C + c];
+      sdl[i] = g;
+    }
+    __syncthreads();
+    for (int r = wave; r < rows; r += FF_WAVES) {
+      float* dx = dX + (t0 + r) * D;
+      for (int k = lane; k < D; k += 64) {
+        float a = 0.f;
+        for (int c = 0; c < C; ++c) a = fmaf(sdl[r * C + c], W[static_cast<int64_t>(c) * D + k], a);
+        dx[k] = a;
+      }
+    }
+    for (int i = threadIdx.x; i < width; i += FF_THREADS) {
+      float a = out[i];
+      if (i < C * D) {
+        const int c = i / D, k = i - c * D;
+        for (int r = 0; r < rows; ++r) a = fmaf(sdl[r * C + c], X[(t0 + r) * D + k], a);
+      } else {
+        const int c = i - C * D;
+        for (int r = 0; r < rows; ++r) a += sdl[r * C + c];
+      }
+      out[i] = a;
+    }
+  }
+}
+
+int64_t ff_cls_blocks(int64_t N) {
+  int64_t nb = ebn_ceil_div(N, FF_CLS_TILE);
+  if (nb > FF_CLS_MAX_PARTS) nb = FF_CLS_MAX_PARTS;
+  return nb < 1 ? 1 : nb;
+}
+
+int ff_cls_check(int64_t N, int32_t D, int32_t C) {
+  EBN_REQUIRE(N >= 0 && D > 0 && C > 0, EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(C <= FF_CLS_MAX_C && D <= FF_CLS_MAX_D && N <= EBN_DIM_MAX && ebn_sat_mul(N, D) < (int64_t(1) << 40), EBN_ERR_UNSUPPORTED);
+  return EBN_OK;
 }
 
 // ---- fast additive attention core (FfAttn and the softmax routines: ebn_ff_attn.h) ------------------------------------------------
@@ -774,6 +930,58 @@ extern "C" int ebn_ff_attn_bwd_f32(const float* Q, const float* K, const float* 
   // n_seq == 0: one workgroup writes one zero partial
   EBN_LAUNCH(ff_attn_bwd_kernel, dim3(static_cast<uint32_t>(grid)), dim3(FF_THREADS),
              static_cast<size_t>(ff_attn_bwd_lds_floats(T, D, heads)) * sizeof(float), ebn_stream(stream), a);
+  EBN_CHECK_LAUNCH();
+  return EBN_OK;
+}
+
+extern "C" int ebn_ff_ln_pos_fwd_f32(const float* X, const float* bias, const float* pos, const float* gamma, const float* beta,
+                                     float eps, uint32_t drop_key, float drop_p, float* Y, float* xhat, float* rstd, int64_t n_seq,
+                                     int32_t T, int32_t D, ebn_stream_t stream) {
+  EBN_REQUIRE(X && pos && gamma && beta && Y, EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(drop_p >= 0.f && drop_p < 1.f, EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(n_seq >= 0 && T > 0, EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(n_seq <= EBN_DIM_MAX && ebn_sat_mul(n_seq, T) <= EBN_DIM_MAX, EBN_ERR_UNSUPPORTED);
+  const int64_t R = n_seq * T;
+  const int rc = ff_ln_check(R, D, 0);
+  if (rc != EBN_OK) return rc;
+  if (R == 0) return EBN_OK;
+  EBN_LAUNCH(ff_ln_pos_fwd_kernel, dim3(static_cast<uint32_t>(ebn_ceil_div(R, FF_WAVES))), dim3(FF_THREADS), 0, ebn_stream(stream), X,
+             bias, pos, gamma, beta, eps, ff_make_drop(drop_key, drop_p), Y, xhat, rstd, R, T, D);
+  EBN_CHECK_LAUNCH();
+  return EBN_OK;
+}
+
+extern "C" int ebn_ff_cls_fwd_f32(const float* X, const float* W, const float* b, const int64_t* targets, float* logits, float* prob,
+                                  float* rowloss, float* loss, int32_t* flag, int64_t N, int32_t D, int32_t C, ebn_stream_t stream) {
+  EBN_REQUIRE(X && W && b && targets && logits && prob && rowloss && loss && flag, EBN_ERR_BAD_ARG);
+  const int rc = ff_cls_check(N, D, C);
+  if (rc != EBN_OK) return rc;
+  if (N > 0) {
+    EBN_LAUNCH(ff_cls_fwd_kernel, dim3(static_cast<uint32_t>(ebn_ceil_div(N, FF_WAVES))), dim3(FF_THREADS), 0, ebn_stream(stream), X,
+               W, b, targets, logits, prob, rowloss, flag, N, D, C);
+    EBN_CHECK_LAUNCH();
+  }
+  EBN_LAUNCH(ff_cls_loss_kernel, dim3(1), dim3(FF_THREADS), 0, ebn_stream(stream), rowloss, loss, N);
+  EBN_CHECK_LAUNCH();
+  return EBN_OK;
+}
+
+extern "C" int64_t ebn_ff_cls_partials_len(int64_t N, int32_t D, int32_t C) {
+  if (!ebn_dim_ok(N, D, C) || D > FF_CLS_MAX_D || C > FF_CLS_MAX_C) return 0;
+  return ff_cls_blocks(N) * (static_cast<int64_t>(C) * D + C);
+}
+
+extern "C" int ebn_ff_cls_bwd_f32(const float* X, const float* W, const float* prob, const int64_t* targets, const float* dloss,
+                                  const float* dscore, float* dX, float* partials, int32_t* n_parts, int64_t N, int32_t D, int32_t C,
+                                  ebn_stream_t stream) {
+  EBN_REQUIRE(X && W && prob && targets && dX && partials && n_parts, EBN_ERR_BAD_ARG);
+  const int rc = ff_cls_check(N, D, C);
+  if (rc != EBN_OK) return rc;
+  const int64_t nb = ff_cls_blocks(N);
+  *n_parts = static_cast<int32_t>(nb);
+  // N == 0 still writes one (zero) partial: the finishing pass then yields zero gradients
+  EBN_LAUNCH(ff_cls_bwd_kernel, dim3(static_cast<uint32_t>(nb)), dim3(FF_THREADS), 0, ebn_stream(stream), X, W, prob, targets, dloss,
+             dscore, dX, partials, N, D, C, ebn_ceil_div(N > 0 ? N : 1, nb));
   EBN_CHECK_LAUNCH();
   return EBN_OK;
 }

@@ -290,7 +290,7 @@ class _Engine:
         m = self.m
         N, H, T = hist.shape
         self.T = T
-        D, heads, I = self.D, self.heads, self.I
+        D = self.D
         dev = hist.device
         table = m.word_embedding.weight
         V, E = table.shape
@@ -309,8 +309,31 @@ class _Engine:
         enc = m.news_encoder
         h, xhat0, rstd0 = self.ln_fwd(Z, m.embedding_transform.bias, enc.position_embeddings.weight, enc.LayerNorm, 0, keys[0], p, keep)
         del Z
+        h, saved_layers = self.layers_fwd(enc.encoders, h, mask, n_seq, T, p, keys, keep, attn_fwd)
+        NV, sv_tok = self.pool_fwd(h, enc.poolers[0], mask, n_seq, T)
+        HV = NV[:N * H]
+        user, sv_user = self.pool_fwd(HV, m.user_attention_polling, hmask, N, H)
+        CV = NV[N * H:]
+        score = torch.empty(N, device=dev)
+        self.call("ebn_ff_head_fwd_f32", ptr(user), ptr(CV), ptr(m.output_layer.weight), ptr(m.output_layer.bias), ptr(score), N, D, S())
+        if int(oob.item()) != 0:
+            raise IndexError(f"token id outside the word table [0, {V})")
+        saved = None
+        if keep:
+            saved = dict(N=N, H=H, T=T, ids=ids, X0=X0, xhat0=xhat0, rstd0=rstd0, layers=saved_layers, hL=h, NV=NV, sv_tok=sv_tok,
+                         user=user, sv_user=sv_user, score=score, p=p, keys=keys, attention=kind)
+        return score, saved, (user, NV)
+
+    def layers_fwd(self, encoders, h, mask, n_seq, T, p, keys, keep, attn_fwd):
+        """The FastformerLayer stack over h [n_seq*T, D] (shared with fastformer_wu.py) -> (h, what the backward needs per layer)."""
+        from ebrec._hip import ptr, stream_handle
+
+        D, heads, I = self.D, self.heads, self.I
+        dev = h.device
+        R = n_seq * T
+        S = stream_handle
         saved_layers = []
-        for l, layer in enumerate(enc.encoders):
+        for l, layer in enumerate(encoders):
             at = layer.attention.self
             Q = self.linear(h, at.query.weight, torch.empty(R, D, device=dev))
             K = self.linear(h, at.key.weight, torch.empty(R, D, device=dev))
@@ -334,29 +357,16 @@ class _Engine:
             if keep:
                 saved_layers.append((h, Q, K, AO, SV, qw, kw, pq, pk, xh1, rs1, A1, I1, G, xh2, rs2))
             h = hn
-        NV, sv_tok = self.pool_fwd(h, enc.poolers[0], mask, n_seq, T)
-        HV = NV[:N * H]
-        user, sv_user = self.pool_fwd(HV, m.user_attention_polling, hmask, N, H)
-        CV = NV[N * H:]
-        score = torch.empty(N, device=dev)
-        self.call("ebn_ff_head_fwd_f32", ptr(user), ptr(CV), ptr(m.output_layer.weight), ptr(m.output_layer.bias), ptr(score), N, D, S())
-        if int(oob.item()) != 0:
-            raise IndexError(f"token id outside the word table [0, {V})")
-        saved = None
-        if keep:
-            saved = dict(N=N, H=H, T=T, ids=ids, X0=X0, xhat0=xhat0, rstd0=rstd0, layers=saved_layers, hL=h, NV=NV, sv_tok=sv_tok,
-                         user=user, sv_user=sv_user, score=score, p=p, keys=keys, attention=kind)
-        return score, saved, (user, NV)
+        return h, saved_layers
 
     def backward(self, sv, dscore, need):
         """-> {parameter name: gradient}"""
-        from ebrec import _hip
         from ebrec._hip import ptr, stream_handle
 
         m = self.m
         N, H, T, p, keys = sv["N"], sv["H"], sv["T"], sv["p"], sv["keys"]
         self.T = T
-        D, heads = self.D, self.heads
+        D = self.D
         n_seq = N * (H + 1)
         R = n_seq * T
         NV = sv["NV"]
@@ -373,11 +383,54 @@ class _Engine:
         self.pool_bwd(HV, m.user_attention_polling, sv["sv_user"], duser, dNV[:N * H], N, H, g, "user_attention_polling.", need)
         dh = torch.empty(R, D, device=dev)
         self.pool_bwd(sv["hL"], enc.poolers[0], sv["sv_tok"], dNV, dh, n_seq, T, g, "news_encoder.poolers.0.", need)
-        for l in range(self.layers - 1, -1, -1):
-            layer = enc.encoders[l]
+        dh = self.layers_bwd(enc.encoders, sv["layers"], dh, n_seq, T, p, keys, sv["attention"], g, "news_encoder.encoders.", need)
+        dZ, _, (dg, dbt, dbias) = self.ln_bwd(dh, sv["xhat0"], sv["rstd0"], enc.LayerNorm, 0, keys[0], p)
+        g["news_encoder.LayerNorm.weight"], g["news_encoder.LayerNorm.bias"], g["embedding_transform.bias"] = dg, dbt, dbias
+        if need("news_encoder.position_embeddings.weight"):
+            dpos = torch.zeros_like(enc.position_embeddings.weight)
+            dpos[0].copy_(dbias)  # only row 0 is ever read
+            g["news_encoder.position_embeddings.weight"] = dpos
+        X0 = sv["X0"]
+        if need("embedding_transform.weight"):
+            g["embedding_transform.weight"] = self.back_weight(dZ, X0)
+        if need("word_embedding.weight"):
+            g["word_embedding.weight"] = self.table_grad(m.word_embedding.weight, sv["ids"], dZ, m.embedding_transform.weight, X0)
+        return g
+
+    def table_grad(self, table, ids, dZ, Wt, X0):
+        """The word table's gradient from dZ [R, D] behind embedding_transform (weight Wt): dX0 = dZ . Wt into X0's buffer (not needed
+        any more), then the fixed-point scatter by ids [R]."""
+        from ebrec import _hip
+        from ebrec._hip import ptr, stream_handle
+
+        V, E = table.shape
+        R, dev = X0.shape[0], X0.device
+        dX0 = self.back_data(dZ, Wt, X0)
+        acc = getattr(self, "_acc", None)
+        if acc is None or acc.numel() != V * E or acc.device != dev:
+            acc = self._acc = torch.zeros(V * E, dtype=torch.int64, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        dT = torch.empty(V, E, device=dev)
+        _hip.call("ebn_embedding_grad_scatter_fixed", ptr(ids), ptr(dX0), ptr(acc), R, E, V, None, -1, _f(0), ptr(flag), stream_handle())
+        _hip.call("ebn_fixed_to_f32", ptr(acc), ptr(dT), V * E, ptr(flag), stream_handle())  # re-zeroes the accumulator
+        if int(flag.item()) != 0:
+            raise FloatingPointError("word-table gradient outside the fixed-point accumulator's range")
+        return dT
+
+    def layers_bwd(self, encoders, saved_layers, dh, n_seq, T, p, keys, kind, g, prefix, need):
+        """The backward of layers_fwd from dh [n_seq*T, D]: parameter gradients into g under `prefix`, -> dL/d(the stack's input)."""
+        from ebrec import _hip
+        from ebrec._hip import ptr, stream_handle
+
+        D, heads = self.D, self.heads
+        R = n_seq * T
+        dev = dh.device
+        S = stream_handle
+        for l in range(len(saved_layers) - 1, -1, -1):
+            layer = encoders[l]
             at, so = layer.attention.self, layer.attention.output
-            h, Q, K, AO, SV, qw, kw, pq, pk, xh1, rs1, A1, I1, G, xh2, rs2 = sv["layers"][l]
-            pre = f"news_encoder.encoders.{l}."
+            h, Q, K, AO, SV, qw, kw, pq, pk, xh1, rs1, A1, I1, G, xh2, rs2 = saved_layers[l]
+            pre = f"{prefix}{l}."
             dO, dA1, (dg, dbt, dbias) = self.ln_bwd(dh, xh2, rs2, layer.output.LayerNorm, 1, keys[2 + 2 * l], p)
             g[pre + "output.LayerNorm.weight"], g[pre + "output.LayerNorm.bias"], g[pre + "output.dense.bias"] = dg, dbt, dbias
             if need(pre + "output.dense.weight"):
@@ -403,7 +456,7 @@ class _Engine:
             dQ, dK = torch.empty(R, D, device=dev), torch.empty(R, D, device=dev)
             n = ctypes.c_int32(0)
             a = pre + "attention.self."
-            if sv["attention"] == "resident":
+            if kind == "resident":
                 width = 2 * heads * D + 3 * D
                 part = torch.empty(int(_hip.lib().ebn_ff_attn_partials_len(n_seq, D, heads)), device=dev)
                 self.call("ebn_ff_attn_bwd_f32", ptr(Q), ptr(K), ptr(at.query_att.weight), ptr(at.key_att.weight), ptr(qw), ptr(kw), ptr(pq), ptr(pk),
@@ -434,30 +487,7 @@ class _Engine:
             self.back_data(dQ, at.query.weight, dh_in, beta=1.0)
             self.back_data(dK, at.key.weight, dh_in, beta=1.0)
             dh = dh_in
-        dZ, _, (dg, dbt, dbias) = self.ln_bwd(dh, sv["xhat0"], sv["rstd0"], enc.LayerNorm, 0, keys[0], p)
-        g["news_encoder.LayerNorm.weight"], g["news_encoder.LayerNorm.bias"], g["embedding_transform.bias"] = dg, dbt, dbias
-        if need("news_encoder.position_embeddings.weight"):
-            dpos = torch.zeros_like(enc.position_embeddings.weight)
-            dpos[0].copy_(dbias)  # only row 0 is ever read
-            g["news_encoder.position_embeddings.weight"] = dpos
-        X0 = sv["X0"]
-        if need("embedding_transform.weight"):
-            g["embedding_transform.weight"] = self.back_weight(dZ, X0)
-        if need("word_embedding.weight"):
-            table = m.word_embedding.weight
-            V, E = table.shape
-            dX0 = self.back_data(dZ, m.embedding_transform.weight, X0)  # X0 is not needed any more
-            acc = getattr(self, "_acc", None)
-            if acc is None or acc.numel() != V * E or acc.device != dev:
-                acc = self._acc = torch.zeros(V * E, dtype=torch.int64, device=dev)
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            dT = torch.empty(V, E, device=dev)
-            _hip.call("ebn_embedding_grad_scatter_fixed", ptr(sv["ids"]), ptr(dX0), ptr(acc), R, E, V, None, -1, _f(0), ptr(flag), S())
-            _hip.call("ebn_fixed_to_f32", ptr(acc), ptr(dT), V * E, ptr(flag), S())  # re-zeroes the accumulator
-            if int(flag.item()) != 0:
-                raise FloatingPointError("word-table gradient outside the fixed-point accumulator's range")
-            g["word_embedding.weight"] = dT
-        return g
+        return dh
 
 
 class _FastformerFn(torch.autograd.Function):

@@ -854,6 +854,35 @@ int ebn_ff_attn_streamed_bwd_f32(const float* Q, const float* K, const float* Wq
                                  float* dK, float* d1, float* d2, float* kp, float* partials, int32_t* n_parts, int64_t n_seq,
                                  int32_t T, int32_t D, int32_t heads, ebn_stream_t stream);
 
+/* ---- Fastformer_wu (reference models/fastformer/fastformer_wu.py): the positional encoder and the class head ---------------------
+ * StandardFastformerEncoder.forward's embedding block (fastformer_wu.py:216-224: position_ids = arange(n_tokens), embeddings =
+ * dropout(LayerNorm(input_embs + position_embeddings))) over n_seq sequences of T tokens, D <= 1024 columns; row r = n * T + t:
+ *   Y [n_seq*T, D] = drop(LN(X + bias + pos[r % T])),  pos [>= T, D]: only rows < T are read.
+ * bias [D] may be NULL (the stand-alone encoder has none; Fastformer_wu folds embedding_transform.bias in, fastformer_wu.py:267).
+ * LN, eps, drop_key / drop_p, xhat [n_seq*T, D] and rstd [n_seq*T] (both may be NULL) as ebn_ff_ln_fwd_f32 mode 0; Y may alias X.
+ * The backward is ebn_ff_ln_bwd_f32 mode 0 (dX and the dgamma | dbeta | dbias partials); the position rows' gradient is the sum of
+ * dX over the sequences, dpos[t] = sum_n dX[n, t] = ebn_ff_colsum_finish_f32(dX, n_seq, T * D, T * D, dpos).                       */
+int ebn_ff_ln_pos_fwd_f32(const float* X, const float* bias, const float* pos, const float* gamma, const float* beta, float eps,
+                          uint32_t drop_key, float drop_p, float* Y, float* xhat, float* rstd, int64_t n_seq, int32_t T, int32_t D,
+                          ebn_stream_t stream);
+/* Fastformer_wu.forward's head (fastformer_wu.py:269-270: score = output_layer(text_vec); loss = CrossEntropyLoss()(score, targets)),
+ * 1 <= C <= 64 classes, D <= 1024 (else EBN_ERR_UNSUPPORTED), one wave per row, two launches:
+ *   logits [N, C] = X [N, D] . W[C, D]^T + b;  prob [N, C] = softmax(logits) with the row maximum subtracted (kept for the backward);
+ *   rowloss [N] = log(sum_c exp(l_c - m)) + m - l_y;  loss[0] = (sum_n rowloss[n]) / N: 256 interleaved chains of ascending n, then a
+ *   fixed halving tree.  targets [N] int64.  A target outside [0, C) sets flag[0] = 1 (the caller zeroes it), its row contributes
+ *   nothing to the sum (N still divides it) and, in the backward, no loss gradient.  No ignore_index, no class weights.            */
+int ebn_ff_cls_fwd_f32(const float* X, const float* W, const float* b, const int64_t* targets, float* logits, float* prob,
+                       float* rowloss, float* loss, int32_t* flag, int64_t N, int32_t D, int32_t C, ebn_stream_t stream);
+/* Its backward from dloss (a DEVICE scalar; NULL = 0) and dscore [N, C] (NULL = 0):
+ *   dlogits = dloss[0] / N * (prob - onehot(target)) + dscore;  dX [N, D] = dlogits . W (c ascending).
+ * dW [C, D] and db [C] are left as *n_parts (a HOST out-parameter, <= 128) per-workgroup partials [n_parts][C * D + C] = dW | db for
+ * ebn_ff_colsum_finish_f32 (stride = width = C * D + C); workgroup g adds its rows in ascending order.  partials:
+ * ebn_ff_cls_partials_len(N, D, C) floats.                                                                                        */
+int64_t ebn_ff_cls_partials_len(int64_t N, int32_t D, int32_t C);
+int ebn_ff_cls_bwd_f32(const float* X, const float* W, const float* prob, const int64_t* targets, const float* dloss,
+                       const float* dscore, float* dX, float* partials, int32_t* n_parts, int64_t N, int32_t D, int32_t C,
+                       ebn_stream_t stream);
+
 /* Step prologue: copy up to three device buffers (history ids, candidate ids, labels of a batch handed over as device
  * tensors -- the inputs of nrms.py:170-176) into the step's static buffers with ONE launch; n_i in bytes, multiples
  * of 4; a NULL source or n_i = 0 skips that pair.                                                                   */
