@@ -5,4 +5,7 @@ from .beyond_accuracy import Calibration, Coverage, Distribution, IntralistDiver
 from .device_metrics import DeviceMetricEvaluator, RaggedLists  # noqa: F401
 from .rerank import DPP, MMR, Calibrated, calibrated_rerank, dpp_rerank, history_distribution, mmr_rerank  # noqa: F401
 from .freshness import Freshness  # noqa: F401
-from .catalogue_ranks import rank_metrics  # noqa: F401
+from .catalogue_ranks import bootstrap_rank_metrics, rank_metrics, rank_values  # noqa: F401
+from .bootstrap import (  # noqa: F401
+    BootstrapResult, PairedBootstrapResult, bootstrap_evaluator, bootstrap_means, paired_bootstrap, poisson_bootstrap_sums,
+)

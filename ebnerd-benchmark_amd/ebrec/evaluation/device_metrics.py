@@ -198,7 +198,10 @@ class DeviceMetricEvaluator(MetricEvaluator):
     ndarray inputs -- AccuracyScore / F1Score binarise the arrays in place, so later metrics see 0 / 1 scores -- is NOT reproduced.
 
     After ``evaluate()``: `sums` {name: sum over impressions} for the slot metrics and `n_impressions`, so that shards combine by
-    addition (mean = sum of sums / sum of counts); with ``evaluate(per_impression=True)`` also `per_impression` {name: values}."""
+    addition (mean = sum of sums / sum of counts); with ``evaluate(per_impression=True)`` also `per_impression` {name: values}.
+    The bootstrap of those values (evaluation/bootstrap.py, ``bootstrap_evaluator``) combines the same way: the `sums` and `weights`
+    ``poisson_bootstrap_sums`` gives two disjoint shards of impressions under one seed and GLOBAL keys (``first_key`` = the shard's
+    first impression number, or ``keys`` = user codes from one dictionary) add up to those of all impressions."""
 
     def __init__(self, labels, predictions, metric_functions, device="cuda"):
         super().__init__(labels, predictions, metric_functions)

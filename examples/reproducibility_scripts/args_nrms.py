@@ -50,6 +50,9 @@ def build_parser(docvec: bool = False) -> argparse.ArgumentParser:
     p.add_argument("--device_metrics", action="store_true",
                    help="validation metrics through DeviceMetricEvaluator and the per-chunk ranking through "
                         "rank_predictions_by_score_ragged (HIP kernels over ragged lists) instead of the per-impression Python loops")
+    p.add_argument("--bootstrap", type=int, default=0,
+                   help="with --device_metrics: print a 95 %% interval beside each validation metric, from this many Poisson-bootstrap "
+                        "resamples over users (ebrec.evaluation.bootstrap); 0 = off")
     p.add_argument("--precision", type=str, default="exact", choices=["exact", "split"],
                    help="exact: every matmul on the exact-fp32 MFMA kernels; split: the news encoder's projection GEMMs as fp32-accurate "
                         "bf16x6 split products on the bf16 matrix pipe (NRMS only)")

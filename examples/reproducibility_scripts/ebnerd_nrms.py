@@ -29,7 +29,8 @@ sys.path.insert(0, str(ROOT / "ebnerd-benchmark_amd"))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from args_nrms import get_args  # noqa: E402
-from ebrec.evaluation import AucScore, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore  # noqa: E402
+from ebrec.evaluation import (AucScore, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore,  # noqa: E402
+                              bootstrap_evaluator)
 from ebrec.models.newsrec import NRMSModel  # noqa: E402
 from ebrec.models.newsrec.callbacks import EarlyStopping, ModelCheckpoint, ReduceLROnPlateau, TensorBoard  # noqa: E402
 from ebrec.models.newsrec.dataloader import NRMSDataLoader, NRMSDataLoaderPretransform  # noqa: E402
@@ -174,15 +175,23 @@ def run(args, hparams, build_model, article_mapping, MODEL_NAME, after_validatio
     pred_val = model.scorer.predict(mk(df_val_eval, True, args.bs_test))
     df_val_eval = add_prediction_scores(df_val_eval, pred_val.tolist())
     labels, scores = df_val_eval[DEFAULT_LABELS_COL].tolist(), df_val_eval["scores"].tolist()
+    users = df_val_eval[DEFAULT_USER_COL].tolist() if DEFAULT_USER_COL in df_val_eval.columns else None
     if world > 1:  # each rank scored its own shard of the held-out day; the metrics are over all of it, on every rank
         parts = [None] * world
-        torch.distributed.all_gather_object(parts, ([list(l) for l in labels], [list(x) for x in scores]))
+        torch.distributed.all_gather_object(parts, ([list(l) for l in labels], [list(x) for x in scores], users))
         labels, scores = [l for p in parts for l in p[0]], [x for p in parts for x in p[1]]
+        users = None if users is None else [u for p in parts for u in p[2]]
     Evaluator = DeviceMetricEvaluator if getattr(args, "device_metrics", False) else MetricEvaluator
-    metrics = Evaluator(labels=labels, predictions=scores,
-                        metric_functions=[AucScore(), MrrScore(), NdcgScore(k=5), NdcgScore(k=10)]).evaluate()
+    n_boot = int(getattr(args, "bootstrap", 0) or 0) if getattr(args, "device_metrics", False) else 0
+    evaluator = Evaluator(labels=labels, predictions=scores, metric_functions=[AucScore(), MrrScore(), NdcgScore(k=5), NdcgScore(k=10)])
+    metrics = evaluator.evaluate(per_impression=True) if n_boot else evaluator.evaluate()
     if rank == 0:
         print(metrics)
+        if n_boot and metrics.per_impression:  # --bootstrap N: whole users are resampled, one user has many impressions
+            boot = bootstrap_evaluator(metrics, n_resamples=n_boot, seed=SEED, clusters=users)
+            unit = "impressions" if users is None else "users"
+            for name, (lo, hi) in boot.ci(0.95).items():
+                print(f"  {name}: {boot.estimate[name]:.6f}  95% CI [{lo:.6f}, {hi:.6f}]  (Poisson bootstrap over {unit}, {n_boot} resamples)")
         write_json_file(metrics.evaluations, ARTIFACT_DIR / "validation_metrics.json")
 
     if after_validation is not None:

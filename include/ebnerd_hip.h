@@ -1284,6 +1284,45 @@ int ebn_calibrated_rerank_f32(const float* W, int64_t n_rows, int32_t C, const i
                               const float* target, int64_t target_stride, int32_t k, float lam, float alpha, int32_t* out_sel,
                               float* out_obj, int32_t* flags, int64_t U, ebn_stream_t stream);
 
+/* ---- Poisson bootstrap of per-item metric columns (no reference counterpart: the interval and the paired test behind every mean
+ * MetricEvaluator and rank_metrics report; Hanley and MacGibbon 2006, Chamandy et al. 2012 for the Poisson form) --------------------
+ * Resample b gives item i the weight w(i, b) ~ Poisson(1) of a counter-based stream, all arithmetic in uint32, lowbias32 the mixer
+ * of the dropout stream:
+ *   k   = lowbias32(seed ^ 0x9E3779B9)
+ *   a_i = lowbias32(key_i ^ k)                key_i = keys[i], or first_key + i when keys is NULL
+ *   r_b = lowbias32((b * 0x9E3779B9) ^ ~k)    b = first_resample + row
+ *   u   = lowbias32(a_i + r_b)
+ *   w   = #{ j : u >= C_j },  C_j = floor(2^32 P(W <= j)) for W ~ Poisson(1), j = 0 .. 11 (EBN_BS_THRESHOLDS; the 13th threshold
+ *         would be 2^32 - 1, so w <= 12)
+ * Items with the same key (a dense cluster code: a user) get the same weight in every resample -- the cluster bootstrap.  The weight
+ * is a function of (seed, key, b) alone, so resamples [first_resample, first_resample + n_resamples) are those rows of any larger
+ * call, and two disjoint item sets with global keys ADD to their union (sums within rounding, weight_sums exactly).
+ *   sums [n_resamples, n_cols] fp64 = sum_i w(i, b) values[c * ld + i];  weight_sums [n_resamples] int64 = sum_i w(i, b), exact.
+ * values [n_cols, ld] fp64 on the device, ld >= n_items; only entries i < n_items of a column are read.  A non-finite value makes
+ * its column's sums NaN (0 * inf): the host layer rejects such input.
+ * Grid: EBN_BS_RESAMPLES resamples per workgroup (two per lane) x up to 512 contiguous item ranges, each a whole number of
+ * EBN_BS_TILE-item tiles staged through LDS (a_i and the column values, read back as broadcasts); the ranges depend on n_items ONLY.
+ * A lane adds its items in ascending order, one fma(w, x, acc) per column; every range writes its partials to the workspace and a
+ * closing launch adds the ranges in ascending order.  No floating-point atomics: two runs give the same bits; a column's bits do
+ * not depend on which other columns share the call, nor a resample's on which other resamples do.
+ * 1 <= n_cols <= EBN_BS_MAX_COLS (EBN_ERR_UNSUPPORTED above); n_items in [0, 2^31 - 257] (0: all sums are 0), n_resamples in
+ * [0, 2^31 - 1] (0: nothing to do), first_resample >= 0 and first_resample + n_resamples <= 2^32, ld >= n_items, NULL values / sums /
+ * weight_sums / workspace, a workspace that is not 16-byte aligned or smaller than the query: EBN_ERR_BAD_ARG.  All checked on the
+ * host before anything is launched.                                                                                               */
+#define EBN_BS_MAX_COLS 16
+#define EBN_BS_TILE 256      /* items of one LDS tile; an item range is a whole number of tiles */
+#define EBN_BS_RESAMPLES 512 /* resamples per workgroup */
+#define EBN_BS_MAX_WEIGHT 12
+#define EBN_BS_THRESHOLDS                                                                                                     \
+  {1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u, 4292415291u, 4294609777u, 4294923276u, 4294962463u, 4294966817u, \
+   4294967252u, 4294967292u}
+/* Bytes of workspace: ranges(n_items) * n_resamples * (n_cols + 1) * 8; 0 for extents outside the limits above, INT64_MAX when the
+ * product does not fit.  Pure host query.                                                                                          */
+int64_t ebn_poisson_bootstrap_workspace_bytes(int64_t n_items, int64_t n_resamples, int32_t n_cols);
+int ebn_poisson_bootstrap_f64(const double* values, int64_t ld, int64_t n_items, int32_t n_cols, const uint32_t* keys,
+                              uint32_t first_key, uint32_t seed, int64_t first_resample, int64_t n_resamples, double* sums,
+                              int64_t* weight_sums, void* workspace, int64_t workspace_bytes, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
