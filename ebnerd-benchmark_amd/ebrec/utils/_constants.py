@@ -17,6 +17,9 @@ DEFAULT_SUBTITLE_COL = "subtitle"
 DEFAULT_BODY_COL = "body"
 DEFAULT_CATEGORY_COL = "category"
 DEFAULT_ARTICLE_PUBLISHED_TIMESTAMP_COL = "published_time"
+DEFAULT_TOTAL_READ_TIME_COL = "total_read_time"
+DEFAULT_TOTAL_PAGEVIEWS_COL = "total_pageviews"
+DEFAULT_TOTAL_INVIEWS_COL = "total_inviews"
 
 # history.parquet
 DEFAULT_HISTORY_ARTICLE_ID_COL = f"{DEFAULT_ARTICLE_ID_COL}_fixed"

@@ -1,0 +1,115 @@
+"""Popularity baselines on an EB-NeRD split (the job of the reference's examples/baseline/ebnerd_feat_baselines.py):
+
+    python examples/baseline/ebnerd_feat_baselines.py --data_path ~/ebnerd_data --datasplit ebnerd_small --device_metrics
+
+Scores the split's validation impressions with every baseline the data has the columns for, prints AUC / MRR / nDCG@5 / nDCG@10 per
+baseline and writes one zipped submission file per baseline into --dump_dir:
+
+  * total_pageviews / total_inviews / total_read_time of articles.parquet (``ArticleFeatureBaseline``) and the in-view frequency of
+    the evaluated frame (``InviewEstimateBaseline``): the reference script's four lookups, totals over the whole dataset;
+  * recent_popularity: clicks in the 1 h / 6 h / 24 h before each impression (``RecentPopularity``), counted over the train
+    behaviours, the train history when it carries its times, and -- with --index_validation_clicks -- the evaluated impressions'
+    own clicks (the window ends before the impression's own time, so an impression never sees its own click).
+
+With --device_metrics the counts, the ranking and the metrics run on the GPU; without it everything runs on the host."""
+from __future__ import annotations
+
+import argparse
+import datetime as dt
+import sys
+from pathlib import Path
+
+import numpy as np
+import pandas as pd
+
+ROOT = Path(__file__).resolve().parents[2]
+sys.path.insert(0, str(ROOT / "ebnerd-benchmark_amd"))
+
+from ebrec.evaluation import AucScore, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore, RaggedLists  # noqa: E402
+from ebrec.models import ArticleFeatureBaseline, InviewEstimateBaseline, PopularityIndex, RecentPopularity  # noqa: E402
+from ebrec.utils._constants import (DEFAULT_CLICKED_ARTICLES_COL, DEFAULT_HISTORY_ARTICLE_ID_COL,  # noqa: E402
+                                    DEFAULT_HISTORY_IMPRESSION_TIMESTAMP_COL, DEFAULT_IMPRESSION_ID_COL, DEFAULT_IMPRESSION_TIMESTAMP_COL,
+                                    DEFAULT_INVIEW_ARTICLES_COL, DEFAULT_TOTAL_INVIEWS_COL, DEFAULT_TOTAL_PAGEVIEWS_COL,
+                                    DEFAULT_TOTAL_READ_TIME_COL)
+from ebrec.utils._python import rank_predictions_by_score_ragged, write_submission_file  # noqa: E402
+
+WINDOWS = [dt.timedelta(hours=1), dt.timedelta(hours=6), dt.timedelta(hours=24)]
+FEATURES = {"clicked_prediction_scores": DEFAULT_TOTAL_PAGEVIEWS_COL, "inview_prediction_scores": DEFAULT_TOTAL_INVIEWS_COL,
+            "readtime_prediction_scores": DEFAULT_TOTAL_READ_TIME_COL}
+
+
+def get_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--data_path", default="~/ebnerd_data")
+    ap.add_argument("--datasplit", default="ebnerd_demo")
+    ap.add_argument("--dump_dir", default="ebnerd_predictions/baselines")
+    ap.add_argument("--device_metrics", action="store_true", help="counts, ranks and metrics on the GPU")
+    ap.add_argument("--index_validation_clicks", action="store_true", help="count the evaluated impressions' earlier clicks too")
+    return ap.parse_args(argv)
+
+
+def labels_of(df) -> RaggedLists:
+    """1 where an in-view article was clicked, aligned with the in-view lists"""
+    inview = RaggedLists.from_lists([np.asarray(x) for x in df[DEFAULT_INVIEW_ARTICLES_COL]], dtype=np.int64)
+    clicked = RaggedLists.from_lists([np.asarray(x) for x in df[DEFAULT_CLICKED_ARTICLES_COL]], dtype=np.int64)
+    ids, codes = np.unique(np.concatenate([inview.flat, clicked.flat]), return_inverse=True)
+    of_list = lambda r: np.repeat(np.arange(len(r), dtype=np.int64), r.lengths) * len(ids)  # (list, article) as one integer
+    n = len(inview.flat)
+    labels = np.isin(of_list(inview) + codes[:n], of_list(clicked) + codes[n:])
+    return RaggedLists(labels.astype(np.int64), inview.offsets)
+
+
+def main(argv=None):
+    args = get_args(argv)
+    device = "cuda" if args.device_metrics else None
+    PATH = Path(args.data_path).expanduser()
+    df_articles = pd.read_parquet(PATH / "articles.parquet")
+    df_train = pd.read_parquet(PATH / args.datasplit / "train" / "behaviors.parquet")
+    df_history = pd.read_parquet(PATH / args.datasplit / "train" / "history.parquet")
+    df = pd.read_parquet(PATH / args.datasplit / "validation" / "behaviors.parquet")
+
+    baselines, skipped = {}, {}
+    for name, column in FEATURES.items():
+        if column in df_articles.columns:
+            baselines[name] = ArticleFeatureBaseline(df_articles, column).predict
+        else:
+            skipped[name] = f"articles.parquet has no column '{column}'"
+    baselines["inview_estimate_prediction_scores"] = InviewEstimateBaseline().predict
+    if DEFAULT_IMPRESSION_TIMESTAMP_COL in df_train.columns and DEFAULT_IMPRESSION_TIMESTAMP_COL in df.columns:
+        parts = [PopularityIndex.from_behaviors(df_train, events="clicks")]
+        if {DEFAULT_HISTORY_ARTICLE_ID_COL, DEFAULT_HISTORY_IMPRESSION_TIMESTAMP_COL} <= set(df_history.columns):
+            parts.append(PopularityIndex.from_history(df_history))
+        else:
+            print(f"recent_popularity: history.parquet has no column '{DEFAULT_HISTORY_IMPRESSION_TIMESTAMP_COL}', counting the behaviours only")
+        if args.index_validation_clicks:
+            parts.append(PopularityIndex.from_behaviors(df, events="clicks"))
+        index = PopularityIndex.concat(*parts)
+        print(f"recent_popularity: {index.n_events} click events of {len(index)} articles, windows 1 h / 6 h / 24 h")
+        baselines["recent_popularity_prediction_scores"] = RecentPopularity(index, WINDOWS, device=device).predict
+    else:
+        skipped["recent_popularity_prediction_scores"] = f"behaviors.parquet has no column '{DEFAULT_IMPRESSION_TIMESTAMP_COL}'"
+    for name, why in skipped.items():
+        print(f"skipped {name}: {why}")
+
+    labels = labels_of(df)
+    metrics = [AucScore(), MrrScore(), NdcgScore(k=5), NdcgScore(k=10)]
+    dump = Path(args.dump_dir)
+    dump.mkdir(parents=True, exist_ok=True)
+    results = {}
+    for name, predict in baselines.items():
+        scores = predict(df)
+        if args.device_metrics:
+            ev = DeviceMetricEvaluator(labels, scores, metrics, device=device).evaluate()
+        else:
+            ev = MetricEvaluator(labels.to_lists(), scores.to_lists(), metrics).evaluate()
+        results[name] = ev.evaluations
+        print(f"{name}: " + "  ".join(f"{k} {v:.4f}" for k, v in ev.evaluations.items()))
+        print("Writing submission file for:", name)
+        write_submission_file(impression_ids=df[DEFAULT_IMPRESSION_ID_COL].tolist(),
+                              prediction_scores=rank_predictions_by_score_ragged(scores, device=device),
+                              path=dump / "predictions.txt", filename_zip=f"{name}.zip")
+    return results, skipped
+
+
+if __name__ == "__main__":
+    main()

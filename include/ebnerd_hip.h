@@ -1323,6 +1323,39 @@ int ebn_poisson_bootstrap_f64(const double* values, int64_t ld, int64_t n_items,
                               uint32_t first_key, uint32_t seed, int64_t first_resample, int64_t n_resamples, double* sums,
                               int64_t* weight_sums, void* workspace, int64_t workspace_bytes, ebn_stream_t stream);
 
+/* ---- trailing-window event counts: time-aware popularity (the baseline beside examples/baseline/ebnerd_feat_baselines.py of the
+ * reference, whose total_pageviews / total_inviews lookups count over the whole dataset and so see every impression's future) ------
+ * EVENTS: the events (clicks, in-views) of article row r are event_times[row_offsets[r] .. row_offsets[r + 1]), ascending int64
+ * times in any unit, equal times allowed; row_offsets [n_rows + 1] int64, a row holds fewer than 2^31 events.
+ * ITEMS: item i of n_items (an in-view article of an impression) asks for row item_rows[i] and belongs to list l with
+ * list_offsets[l] <= i < list_offsets[l + 1] (list_offsets [n_lists + 1] int64 ascending, list_offsets[0] = 0,
+ * list_offsets[n_lists] >= n_items; empty lists anywhere); its query time is t = list_times[l].
+ *   counts[w * ld + i] = #{ e in row item_rows[i] : t - max_age_w <= e < t - min_age }      w < n_windows, i < n_items, int32
+ * The interval is HALF-OPEN AT THE TOP: with min_age = 0 an event at the impression's own time is not counted, so an index that
+ * holds the evaluated impressions' own clicks does not leak them into their scores.  (Freshness, ebn_topk_score_window_f32's host
+ * side, admits  t - max_age <= p <= t - min_age, closed: an article published at the impression's instant may be shown.)
+ * t - max_age and t - min_age SATURATE at INT64_MIN, they do not wrap; max_age = EBN_WC_UNBOUNDED: the window has no lower end.
+ * A window whose max_age <= min_age counts 0.  The windows may come in any order, with duplicates; unused max_age arguments
+ * (w >= n_windows) are ignored.  They are passed BY VALUE, not as an array: every pointer of this ABI is a device pointer, the
+ * ages must be checked (and sorted) on the host, and as kernel arguments they cost no upload and no load.
+ * An item_rows[i] outside [0, n_rows) counts 0 in every window and reads nothing (-1 is the host layer's "unknown article").
+ * Only counts[w * ld + i] for i < n_items, w < n_windows is written; nothing of the inputs past their extents is read.
+ * One lane per item, 256-item workgroups: one upper_bound over list_offsets per workgroup, its next 256 list boundaries staged in
+ * LDS; per item one lower_bound for t - min_age over the row, then one per window inside [previous result, that position), the
+ * windows visited in descending max_age; the two searches over the whole row (the upper end, the longest bounded window) share one
+ * loop.  All compares and indices int64.  No atomics, no workspace: two runs give the same bits.
+ * n_windows outside [1, EBN_WC_MAX_WINDOWS], ld < n_items, n_items / n_lists / n_rows outside [0, 2^31 - 1], min_age < 0, a
+ * max_age_w < 0 (w < n_windows), n_items > 0 with n_lists = 0, NULL item_rows / list_offsets / list_times / counts with n_items > 0,
+ * NULL event_times / row_offsets with n_items > 0 and n_rows > 0: EBN_ERR_BAD_ARG.  n_items == 0: nothing to do.  All checked on the
+ * host before the launch: a failing call writes nothing.                                                                          */
+#define EBN_WC_MAX_WINDOWS 8
+#define EBN_WC_UNBOUNDED INT64_MAX /* a max_age: the window has no lower end */
+int ebn_window_counts_i32(const int64_t* event_times, const int64_t* row_offsets, int64_t n_rows, const int32_t* item_rows,
+                          int64_t n_items, const int64_t* list_offsets, const int64_t* list_times, int64_t n_lists,
+                          int32_t n_windows, int64_t max_age0, int64_t max_age1, int64_t max_age2, int64_t max_age3,
+                          int64_t max_age4, int64_t max_age5, int64_t max_age6, int64_t max_age7, int64_t min_age,
+                          int32_t* counts, int64_t ld, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
