@@ -1,3 +1,7 @@
+from .content import (  # noqa: F401
+    ContentSimilarity, content_centroid_scores_host, content_nearest_scores_host, content_profiles_host, history_weight_values,
+    unit_rows_host,
+)
 from .popularity import (  # noqa: F401
     ArticleFeatureBaseline, InviewEstimateBaseline, PopularityIndex, RecentPopularity, WindowCounts, lexicographic_scores,
     window_counts_host,

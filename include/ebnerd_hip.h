@@ -1356,6 +1356,51 @@ int ebn_window_counts_i32(const int64_t* event_times, const int64_t* row_offsets
                           int64_t max_age4, int64_t max_age5, int64_t max_age6, int64_t max_age7, int64_t min_age,
                           int32_t* counts, int64_t ld, ebn_stream_t stream);
 
+/* ---- content-similarity baselines: "recommend what looks like what this user read", from the document vectors alone (the reference
+ * has no content baseline; the float64 brute force of tests/content_cases.py is the yardstick) ------------------------------------
+ * TABLE: table [n_rows, D] fp32 at row stride ld >= D.  The kernels use the rows AS THEY ARE: the host passes unit rows (what
+ * ebn_ba_unit_rows_f32 leaves), so the dots are cosines.  16-byte loads are used only where the pointer and ld allow them; the bits
+ * of the results do not depend on ld or on the alignment.  D <= EBN_CS_MAX_D.
+ * HISTORIES: history u of n_hists (one per USER, shared by all of the user's impressions) holds the entries
+ * [hist_offsets[u], hist_offsets[u + 1]) of hist_rows [n_hist_items] int32, oldest first; hist_offsets [n_hists + 1] int64
+ * ascending from 0 to at most n_hist_items.  Entry j weighs hist_weights[j] (finite and >= 0: the host's guarantee; used as it is),
+ * or 1 when hist_weights is NULL.
+ * LISTS: list l of n_lists (an impression) holds the items [cand_offsets[l], cand_offsets[l + 1]) of cand_rows [n_cand_items] int32
+ * (cand_offsets [n_lists + 1] int64 ascending from 0 to n_cand_items; empty lists anywhere) and reads history
+ * u(l) = list_hist ? list_hist[l] : l.
+ * An entry or item whose row is outside [0, n_rows) is ABSENT (-1 is the host layer's "unknown article"): its row is never turned
+ * into an address.  Columns >= D of a row and of a profile are never read, nothing of the other operands past its extent is read,
+ * and only the outputs named below are written.
+ *   ebn_cs_profiles_f32:         profiles[u * ldp + k] = p_k / ||p||,  p = sum over the present entries j of history u of
+ *                                w_j * table[hist_rows[j], :];  a ZERO row when no entry is present or ||p|| is 0.  k < D, u < n_hists.
+ *   ebn_cs_centroid_scores_f32:  scores[i] = profiles[u(l), :] . table[cand_rows[i], :] for item i of list l; 0 when the item is
+ *                                absent or u(l) is outside [0, n_hists).  profiles [n_hists, D] at row stride ldp.
+ *   ebn_cs_nearest_scores_f32:   scores[i] = max over the present entries j of history u(l) of w_j * (table[hist_rows[j], :] .
+ *                                table[cand_rows[i], :]); 0 when the item is absent, u(l) is outside [0, n_hists) or the history
+ *                                has no present entry.
+ * profiles: one workgroup per history, its 4 waves take the entries round-robin, partial sums added through LDS in wave order, one
+ * division per element.  centroid: one wave per list, the profile row in registers, one 64-lane sum per item, coalesced stores.
+ * nearest: one workgroup per list, 16 candidate rows per LDS tile (16 * ceil(D / 256) * 1 KiB of dynamic LDS, 64 KiB at the most),
+ * each wave streams its share of the history rows once per tile and keeps a running max per candidate.  Lane ownership of the
+ * columns and every summation order are fixed.  No atomics, no workspace: two runs give the same bits.
+ * D < 1, ld < D, ldp < D, any of n_rows / D / ld / ldp / n_hists / n_hist_items / n_lists / n_cand_items outside [0, 2^31 - 1],
+ * n_cand_items > 0 with n_lists = 0, n_hist_items > 0 with n_hists = 0: EBN_ERR_BAD_ARG; then D > EBN_CS_MAX_D: EBN_ERR_UNSUPPORTED.
+ * Nothing to do (EBN_OK, no launch): n_hists == 0 for the profiles, n_cand_items == 0 for the scores.  Otherwise a NULL among the
+ * pointers the call needs is EBN_ERR_BAD_ARG; hist_weights and list_hist may be NULL, table may be NULL with n_rows == 0 (every
+ * entry is absent), hist_rows with n_hist_items == 0, profiles (an input) and hist_offsets of the score calls with n_hists == 0.
+ * All checked on the host before the launch: a failing call writes nothing.                                                         */
+#define EBN_CS_MAX_D 1024
+int ebn_cs_profiles_f32(const float* table, int64_t n_rows, int64_t D, int64_t ld, const int32_t* hist_rows, const float* hist_weights,
+                        const int64_t* hist_offsets, int64_t n_hists, int64_t n_hist_items, float* profiles, int64_t ldp,
+                        ebn_stream_t stream);
+int ebn_cs_centroid_scores_f32(const float* table, int64_t n_rows, int64_t D, int64_t ld, const float* profiles, int64_t n_hists,
+                               int64_t ldp, const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets,
+                               int64_t n_lists, int64_t n_cand_items, float* scores, ebn_stream_t stream);
+int ebn_cs_nearest_scores_f32(const float* table, int64_t n_rows, int64_t D, int64_t ld, const int32_t* hist_rows,
+                              const float* hist_weights, const int64_t* hist_offsets, int64_t n_hists, int64_t n_hist_items,
+                              const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets, int64_t n_lists,
+                              int64_t n_cand_items, float* scores, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
