@@ -781,6 +781,33 @@ int check_args(const ebn_dvn_args* a) {
   return EBN_OK;
 }
 
+// Everything a call dereferences, checked in front of its FIRST launch: a refused call has written nothing (no half-run step, `stat`
+// as it was).  NULL first (EBN_ERR_BAD_ARG), then the 16-byte alignment of every pointer the kernels access as float4 or as 64-bit
+// words (EBN_ERR_ALIGN); the per-column vectors (b, gamma, beta, the moving statistics, ggamma, gbeta) are read element-wise.
+int check_fwd_ptrs(const ebn_dvn_args* a) {
+  const int L = a->n_layers;
+  EBN_REQUIRE(a->X0 != nullptr && a->NE != nullptr && a->stat != nullptr, EBN_ERR_BAD_ARG);
+  for (int l = 0; l <= L; ++l) EBN_REQUIRE(a->W[l] != nullptr && a->b[l] != nullptr, EBN_ERR_BAD_ARG);
+  for (int l = 0; l < L; ++l)
+    EBN_REQUIRE(a->R[l] && a->Xn[l] && a->gamma[l] && a->beta[l] && a->moving_mean[l] && a->moving_var[l], EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(ebn_aligned16(a->X0) && ebn_aligned16(a->NE) && ebn_aligned16(a->stat), EBN_ERR_ALIGN);
+  for (int l = 0; l <= L; ++l) EBN_REQUIRE(ebn_aligned16(a->W[l]), EBN_ERR_ALIGN);
+  for (int l = 0; l < L; ++l) EBN_REQUIRE(ebn_aligned16(a->R[l]) && ebn_aligned16(a->Xn[l]), EBN_ERR_ALIGN);
+  return EBN_OK;
+}
+
+int check_bwd_ptrs(const ebn_dvn_args* a) {
+  const int L = a->n_layers;
+  EBN_REQUIRE(a->dNE != nullptr && a->NE != nullptr && a->stat != nullptr && a->dP[L] != nullptr, EBN_ERR_BAD_ARG);
+  for (int l = 1; l <= L; ++l) EBN_REQUIRE(a->W[l] != nullptr, EBN_ERR_BAD_ARG);
+  for (int l = 0; l < L; ++l)
+    EBN_REQUIRE(a->R[l] && a->dY[l] && a->dP[l] && a->gamma[l] && a->ggamma[l] && a->gbeta[l], EBN_ERR_BAD_ARG);
+  EBN_REQUIRE(ebn_aligned16(a->dNE) && ebn_aligned16(a->NE) && ebn_aligned16(a->stat) && ebn_aligned16(a->dP[L]), EBN_ERR_ALIGN);
+  for (int l = 1; l <= L; ++l) EBN_REQUIRE(ebn_aligned16(a->W[l]), EBN_ERR_ALIGN);
+  for (int l = 0; l < L; ++l) EBN_REQUIRE(ebn_aligned16(a->R[l]) && ebn_aligned16(a->dY[l]) && ebn_aligned16(a->dP[l]), EBN_ERR_ALIGN);
+  return EBN_OK;
+}
+
 }  // namespace
 
 extern "C" int ebn_dvn_supported(const ebn_dvn_args* a) { return check_args(a) == EBN_OK ? 1 : 0; }
@@ -791,13 +818,12 @@ extern "C" int64_t ebn_dvn_stat_floats(const ebn_dvn_args* a) {
 }
 
 extern "C" int ebn_dvn_fwd_train_f32(const ebn_dvn_args* a, const ebn_step_state* st, ebn_stream_t stream) {
-  const int rc = check_args(a);
+  int rc = check_args(a);
+  if (rc == EBN_OK) rc = check_fwd_ptrs(a);  // all of it in front of the first launch
   if (rc != EBN_OK) return rc;
-  EBN_REQUIRE(a->X0 != nullptr && a->NE != nullptr && a->stat != nullptr, EBN_ERR_BAD_ARG);
   hipStream_t s = ebn_stream(stream);
   const int L = a->n_layers;
   for (int l = 0; l <= L; ++l) {
-    EBN_REQUIRE(a->W[l] != nullptr && a->b[l] != nullptr, EBN_ERR_BAD_ARG);
     PanelArgs p{};
     p.n0 = a->n0;
     p.n1 = a->n1;
@@ -808,7 +834,6 @@ extern "C" int ebn_dvn_fwd_train_f32(const ebn_dvn_args* a, const ebn_step_state
     p.bias = a->b[l];
     p.C = l < L ? a->R[l] : a->NE;
     p.range_flag = a->range_flag;
-    EBN_REQUIRE(p.C != nullptr, EBN_ERR_BAD_ARG);
     if (l < L) p.out_acc = stat_view(a, l).fwd;
     if (l < L && a->l2 > 0.f) p.l2_part = l2_view(a) + l * L2_SLOTS;
     if (l == 0) {
@@ -818,7 +843,6 @@ extern "C" int ebn_dvn_fwd_train_f32(const ebn_dvn_args* a, const ebn_step_state
     } else {
       const StatView sv = stat_view(a, l - 1);
       const EbnDrop d = ebn_make_drop(st, EBN_SITE_MLP0 + (l - 1), a->drop_p);
-      EBN_REQUIRE(a->gamma[l - 1] && a->beta[l - 1] && a->moving_mean[l - 1] && a->moving_var[l - 1] && a->Xn[l - 1], EBN_ERR_BAD_ARG);
       p.A = a->R[l - 1];
       p.Aout = a->Xn[l - 1];
       p.in_acc = sv.fwd;
@@ -842,14 +866,11 @@ extern "C" int ebn_dvn_fwd_train_f32(const ebn_dvn_args* a, const ebn_step_state
 }
 
 // one launch of the backward: l = n_layers (output Dense) ... 1: dy_{l-1} = dropout-backward(dP_l . W_l^T), dP_l formed on the A operand
-// and written out; l = 0: dP_0 element-wise (+ the L2 term of the loss, + re-zeroing of the forward accumulators)
+// and written out; l = 0: dP_0 element-wise (+ the L2 term of the loss, + re-zeroing of the forward accumulators).  The caller has
+// validated the arguments (check_args + check_bwd_ptrs): nothing is refused between two launches
 static int dvn_bwd_layer(const ebn_dvn_args* a, int32_t l, const ebn_step_state* st, ebn_stream_t stream) {
-  const int rc = check_args(a);
-  if (rc != EBN_OK) return rc;
-  EBN_REQUIRE(a->dNE != nullptr && a->NE != nullptr && a->stat != nullptr, EBN_ERR_BAD_ARG);
   hipStream_t s = ebn_stream(stream);
   const int L = a->n_layers;
-  EBN_REQUIRE(l >= 0 && l <= L, EBN_ERR_BAD_ARG);
   if (l >= 1) {
     const StatView so = stat_view(a, l - 1);
     const EbnDrop d_out = ebn_make_drop(st, EBN_SITE_MLP0 + (l - 1), a->drop_p);
@@ -870,14 +891,12 @@ static int dvn_bwd_layer(const ebn_dvn_args* a, int32_t l, const ebn_step_state*
     p.thresh = d_out.thresh;
     p.scale = d_out.scale;
     p.range_flag = a->range_flag;
-    EBN_REQUIRE(p.B && p.C && p.Aout && p.Rout, EBN_ERR_BAD_ARG);
     if (l == L) {
       p.A = a->dNE;
       p.A2 = a->NE;
       return launch_panel<AX_RELU, true, EPI_DY>(p, s);
     }
     const StatView si = stat_view(a, l);
-    EBN_REQUIRE(a->dY[l] && a->R[l] && a->gamma[l] && a->ggamma[l] && a->gbeta[l], EBN_ERR_BAD_ARG);
     p.A = a->dY[l];
     p.A2 = a->R[l];
     p.in_acc = si.bwd;
@@ -889,7 +908,6 @@ static int dvn_bwd_layer(const ebn_dvn_args* a, int32_t l, const ebn_step_state*
     return launch_panel<AX_DBN, true, EPI_DY>(p, s);
   }
   const StatView s0 = stat_view(a, 0);
-  EBN_REQUIRE(a->dY[0] && a->R[0] && a->gamma[0] && a->ggamma[0] && a->gbeta[0] && a->dP[0], EBN_ERR_BAD_ARG);
   ApplyArgs q{a->n0, a->n1, a->units[0], a->dY[0], a->R[0], s0.bwd, a->gamma[0], s0.mean, s0.istd, a->dP[0], a->ggamma[0], a->gbeta[0]};
   q.zero = reinterpret_cast<float*>(s0.fwd);  // the forward accumulators of all layers, for the next step
   q.zero_n = static_cast<int>(8 * sum_units(a, L));
@@ -905,7 +923,8 @@ static int dvn_bwd_layer(const ebn_dvn_args* a, int32_t l, const ebn_step_state*
 }
 
 extern "C" int ebn_dvn_bwd_f32(const ebn_dvn_args* a, const ebn_step_state* st, ebn_stream_t stream) {
-  const int rc = check_args(a);
+  int rc = check_args(a);
+  if (rc == EBN_OK) rc = check_bwd_ptrs(a);  // all of it in front of the first launch
   if (rc != EBN_OK) return rc;
   for (int l = a->n_layers; l >= 0; --l) {
     const int r = dvn_bwd_layer(a, l, st, stream);
@@ -972,6 +991,10 @@ extern "C" int ebn_docvec_stage_gather_f32(const int32_t* idx0, int64_t n0, cons
               reinterpret_cast<uint32_t*>(labels_dst), static_cast<int>(n_labels), reinterpret_cast<const float4*>(matrix),
               reinterpret_cast<float4*>(X0), din / 4, n_rows, oob_flag, st, beta1, beta2};
   const int64_t items = (n0 + n1) * (din / 4);
+  // n0 = n1 = 0 (labels and step state only): no item is live, but the kernel's clamped item 0 still reads an id through a segment
+  // and a row of the matrix.  Both segments may be NULL in this call: hand it the first words of the matrix as a one-id segment --
+  // device memory the caller owns, at least din >= 4 floats of it; whatever it holds, the id is range-checked and the row discarded
+  if (items == 0) a.s0 = a.s1 = reinterpret_cast<const int32_t*>(matrix);
   int64_t blocks = ebn_ceil_div(items, 512);
   if (blocks * 256 < n_labels) blocks = ebn_ceil_div(n_labels, 256);
   if (blocks < 1) blocks = 1;

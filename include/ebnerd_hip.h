@@ -512,7 +512,11 @@ int ebn_batchnorm2_relu_bwd_f32(const float* dY, const float* xhat, const float*
  * rounding (the column sums are order-independent 64-bit fixed-point accumulations of per-tile sums, the batch variance
  * is E[x^2] - mean^2 in float64 from them, not two-pass over the block): bitwise reproducible run to run.
  *
- * All pointers device, 16-byte aligned, matrices dense row-major.  W[l] is (d_l, u_l) with d_0 = din, W[n_layers] the
+ * All pointers device, matrices dense row-major.  X0, W[], R[], Xn[], NE, dNE, dY[], dP[] and stat are accessed as 16-byte vectors
+ * or 64-bit words and must be 16-byte aligned: EBN_ERR_ALIGN otherwise (the per-column vectors b, gamma, beta, the moving statistics,
+ * ggamma and gbeta only 4-byte).  A NULL among the pointers a call uses is EBN_ERR_BAD_ARG, a shape outside ebn_dvn_supported
+ * EBN_ERR_UNSUPPORTED.  Both calls validate EVERYTHING in front of their first launch: a refused call has launched nothing and
+ * written nothing, `stat` included.  W[l] is (d_l, u_l) with d_0 = din, W[n_layers] the
  * output kernel (u_last, e_out); b[l] likewise.  Forward writes R[l] = relu(Dense_l), Xn[l] = Dropout(BN(R[l])), NE, the
  * batch statistics (inside `stat`) and the moving statistics.  Backward reads dNE and writes dY[l] = d(Xn[l]) with the
  * dropout mask applied, dP[l] = d(pre-activation of Dense l) for l = 0..n_layers (the B operands of the weight gradients
@@ -559,7 +563,8 @@ int ebn_dvn_bwd_f32(const ebn_dvn_args* args, const ebn_step_state* st, ebn_stre
 /* The prologue of an NRMSDocVec training step on a device-resident batch of article-row numbers (dataloader.py:169-179,
  * lookup_article_matrix[rows]) as ONE launch: ebn_step_advance (st may be NULL: no advance) + the label copy (n_labels floats) +
  * X0[r,:] = matrix[idx[r],:] for the n0 + n1 rows of the (up to two) index segments idx0 | idx1 -- what ebn_copy3_advance +
- * ebn_gather_rows_f32 do in two.  Rows outside [0, n_rows) write zeros and set *oob_flag (may be NULL).  din % 4 == 0.    */
+ * ebn_gather_rows_f32 do in two.  Rows outside [0, n_rows) write zeros and set *oob_flag (may be NULL).  din % 4 == 0.
+ * An empty segment may be NULL; n0 = n1 = 0 (both NULL) copies the labels, advances the step state and writes nothing else.  */
 int ebn_docvec_stage_gather_f32(const int32_t* idx0, int64_t n0, const int32_t* idx1, int64_t n1, const float* labels_src,
                                 float* labels_dst, int64_t n_labels, const float* matrix, int64_t n_rows, int32_t din, float* X0,
                                 int32_t* oob_flag, ebn_step_state* st, double beta1, double beta2, ebn_stream_t stream);

@@ -35,7 +35,7 @@ and 25 MB per guard for the transposed A (guards are 256 * ld elements, tests/gu
 
 LIMIT: an over-read whose value is discarded by a select never reaches an output and is not detected (tests/guarded.py).
 Zero-scratch contracts are not poisoned: none of the entry points below has one (ebn_dvn_fwd_train_f32's `stat`, the documented
-case, belongs to the DocVec kernels, which are outside this module)."""
+case, belongs to the DocVec kernels: tests/test_guarded_docvec_gpu.py holds them, with `stat` as a guarded zero payload)."""
 import ctypes
 import functools
 
