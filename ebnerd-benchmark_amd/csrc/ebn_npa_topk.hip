@@ -17,8 +17,9 @@
 // to the tile only: a padded token row is never loaded (zeros go into the LDS image, its address stays inside the row's L tokens)
 // and its logit is set to -inf, weight exactly 0.  The K = A phase leaves the logits in 64 accumulator registers, they are turned
 // into e_l in place, the K = F phase fills a second set of 64, and the score is reduced from the two.  Operand staging is
-// ebn_topk.hip's: XOR-swizzled float4 LDS images, 16-deep slabs, two buffers, one barrier per slab.  The selection (survivor queue,
-// sorted insert, write-out, merge of the n_splits partial lists) is ebn_topk_list.h, shared with ebn_topk.hip.
+// ebn_topk.hip's: XOR-swizzled float4 LDS images, 16-deep slabs, two buffers, one barrier per slab.  The whole step up to the score
+// is npa_pooled of ebn_catalogue_walk.h, which npa_rank_kernel (ebn_npa_target_rank.hip) calls as well; the selection (survivor
+// queue, sorted insert, write-out, merge of the n_splits partial lists) is ebn_topk_list.h, shared with ebn_topk.hip.
 //
 // A pair's score bits depend only on the user's two rows and the catalogue row's data: every fma chain, the in-lane reduction order
 // and the (commutative) cross-half add are the same whatever the candidate's position, U, M or n_splits.  Lists are bit-identical for
@@ -32,14 +33,12 @@
 // span.  A wave whose union misses a visited step stages its share of the slabs and takes the barriers -- no MFMA, no expf pass, no
 // selection.  A score is offered only when its position also lies in the lane's window (one unsigned compare; a step inside the
 // wave's intersection takes the plain compare), so nothing outside a window reaches the queue, the NaN flag or the lists.  The
-// score statements are the plain form's: the same bits for the same (user rows, catalogue row) pair.
+// score is the plain form's call of npa_pooled: the same bits for the same (user rows, catalogue row) pair.
+#include "ebn_catalogue_walk.h"
 #include "ebn_topk_list.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int NT_ROW_TILES = TK_BN / 32;  // row tiles (32 token rows each) of a step
 constexpr int NT_MAX_L = 64, NT_MAX_A = 1024, NT_MAX_F = 4096;
 
 struct NpaTopkArgs : TopkList {
@@ -58,15 +57,14 @@ constexpr int NT_WINDOW_LDS_BYTES = 8 * 4;  // (lo, hi) of the four waves' union
 // LT: row tiles of one candidate (1: L <= 32, 2: L <= 64).  dynamic LDS layout: ebn_topk_list.h (WINDOWED: + wave unions[8])
 template <int LT, bool WINDOWED>
 __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) {
-  constexpr int CPS = NT_ROW_TILES / LT;  // candidates of a step
-  constexpr int LP = 32 * LT;             // padded L
+  constexpr int CPS = TK_TILES / LT;  // candidates of a step
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kl = lane >> 5, il = lane & 31;
-  const int k = a.k, L = a.L, F = a.F, A = a.A;
+  const int k = a.k;
   const int64_t u0 = static_cast<int64_t>(blockIdx.x) * TK_BM;
   const int split = blockIdx.y;
   const TopkLds lds = topk_lds(smem, wave, k);
@@ -79,248 +77,48 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
   topk_list_init(lds, k, tid);
   __syncthreads();  // a range without steps (more splits than steps divide into) still writes its empty lists out
 
-  // this thread's two float4 of an operand slab: item v = tid + 256 i -> tile row v / 4, k quarter v % 4
-  const int kq4 = (tid & 3) * 4;
-  const float *pq[2], *pu[2];
-  int sdst[2], tok_c[2], tok_l[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int v = tid + i * TK_THREADS, mn = v >> 2, kq = v & 3;
-    int64_t u = u0 + mn;
-    u = u < a.U ? u : a.U - 1;  // columns past the last user repeat it; their lists are never written out
-    pq[i] = a.Q + u * A + kq4;
-    pu[i] = a.users + u * F + kq4;
-    sdst[i] = (mn * 4 + (kq ^ ((mn >> 2) & 3))) * 4;
-    tok_c[i] = mn / LP;  // candidate of the step
-    tok_l[i] = mn % LP;  // token of the candidate; >= L: padding
-  }
+  const NpaThread th = npa_thread<LT>(a, u0, tid);
   bool saw_nan = false;
 
-  const int64_t n_steps = (a.M + CPS - 1) / CPS;
-  int64_t t_beg = static_cast<int64_t>(split) * a.steps_per_split;
-  int64_t t_end = t_beg + a.steps_per_split;
-  t_end = t_end < n_steps ? t_end : n_steps;
+  int64_t t_beg, t_end;
+  walk_span(a.M, CPS, split, a.steps_per_split, t_beg, t_end);
 
   // WINDOWED: this lane's user (column il of the wave's tile) and its clamped range; a column past the last user repeats the last
-  // user, window included; an empty range is [0, 0): no position passes
+  // user, window included.  The workgroup's union picks the steps
   int lo = 0, hi = 0;
-  int wlo = 0, whi = 0, vlo = 0, vhi = 0, ilo = 0, ihi = 0;
+  WalkSpans sp;
   if constexpr (WINDOWED) {
     const int64_t ul = u0 + wave * 32 + il;
     const bool live = ul < a.U;
-    const int64_t uc = live ? ul : a.U - 1;
-    lo = a.window[2 * uc];
-    hi = a.window[2 * uc + 1];
-    lo = lo > 0 ? lo : 0;
-    hi = static_cast<int64_t>(hi) < a.M ? hi : static_cast<int>(a.M);  // M <= INT32_MAX
-    if (lo >= hi) lo = hi = 0;
-    // the union of this wave [vlo, vhi) over the non-empty windows of its users below U, their intersection [ilo, ihi); the union
-    // of the workgroup [wlo, whi) through LDS.  All of them are wave-uniform.
-    int xlo = INT32_MAX, xhi = 0, nlo = 0, nhi = INT32_MAX;
-    if (live) {
-      if (lo < hi) {
-        xlo = lo;
-        xhi = hi;
-      }
-      nlo = lo;
-      nhi = hi;
-    }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {  // both lane halves hold the same 32 users
-      const int o0 = __shfl_xor(xlo, off, 64), o1 = __shfl_xor(xhi, off, 64), o2 = __shfl_xor(nlo, off, 64), o3 = __shfl_xor(nhi, off, 64);
-      xlo = o0 < xlo ? o0 : xlo;
-      xhi = o1 > xhi ? o1 : xhi;
-      nlo = o2 > nlo ? o2 : nlo;
-      nhi = o3 < nhi ? o3 : nhi;
-    }
-    vlo = __builtin_amdgcn_readfirstlane(xlo);
-    vhi = __builtin_amdgcn_readfirstlane(xhi);
-    ilo = __builtin_amdgcn_readfirstlane(nlo);
-    ihi = __builtin_amdgcn_readfirstlane(nhi);
+    walk_clamp(a.window, live ? ul : a.U - 1, a.M, lo, hi);
     volatile int* wun = lds.lps + TK_BM * k;  // the end of the plan: topk_lds_bytes(k)
-    if (lane == 0) {
-      wun[2 * wave] = vlo;
-      wun[2 * wave + 1] = vhi;
-    }
-    __syncthreads();
-    wlo = INT32_MAX;
-    whi = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int l = wun[2 * w], h = wun[2 * w + 1];
-      wlo = l < wlo ? l : wlo;
-      whi = h > whi ? h : whi;
-    }
-    wlo = __builtin_amdgcn_readfirstlane(wlo);
-    whi = __builtin_amdgcn_readfirstlane(whi);
-    // the steps that meet the union (none: wlo = INT32_MAX, whi = 0), dealt evenly over the splits
-    const int64_t w_beg = wlo / CPS, w_end = wlo < whi ? (static_cast<int64_t>(whi) + CPS - 1) / CPS : w_beg;
-    const int64_t w_n = w_end - w_beg;
-    t_beg = w_beg + w_n * split / a.n_splits;
-    t_end = w_beg + w_n * (split + 1) / a.n_splits;
+    sp = walk_spans_lane(lo, hi, live, wun, wave, lane);
+    walk_span(sp, CPS, split, a.n_splits, t_beg, t_end);
   }
 
   for (int64_t t = t_beg; t < t_end; ++t) {
     const int64_t n0 = t * CPS;
     __syncthreads();  // every wave is done with the previous step's candrow (and the lists are initialised)
-    if (tid < CPS) {
-      const int64_t c = n0 + tid;
-      int row = -2;  // past the last candidate
-      if (c < a.M) {
-        const int64_t r = a.cand_rows != nullptr ? static_cast<int64_t>(a.cand_rows[c]) : c;
-        if (r < 0 || r >= a.n_rows) {
-          row = -1;  // never turned into an address
-          if (!WINDOWED || (c >= wlo && c < whi)) a.flags[0] = 1;  // a visited step also has positions outside the union
-        } else {
-          row = static_cast<int>(r);
-        }
-      }
-      candrow[tid] = row;
-    }
+    walk_rows<WINDOWED>(a, sp, n0, CPS, tid, candrow);
     __syncthreads();
-    // token rows of this thread: a padded token (tok_l >= L) points at the row's token 0 and is never loaded
-    const float *pa[2], *pv[2];
-    bool tok_ok[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = candrow[tok_c[i]];
-      tok_ok[i] = tok_l[i] < L;
-      const int64_t tok = static_cast<int64_t>(r > 0 ? r : 0) * L + (tok_ok[i] ? tok_l[i] : 0);
-      pa[i] = a.Ua + tok * A + kq4;
-      pv[i] = a.Vd + tok * F + kq4;
-    }
 
-    // WINDOWED: a wave none of whose users' windows meets the step fills the operand images and takes the barriers, nothing else
-    const bool wave_on = !WINDOWED || (n0 < vhi && n0 + CPS > vlo);
-
-    // acc[j][r] = sum_k tokens[32 j + row(r, kl)][k] * users[32 wave + il][k]: tokens through ptok, this workgroup's users through pusr
-    auto gemm = [&](const float* const(&ptok)[2], const float* const(&pusr)[2], const int K, f32x16(&acc)[NT_ROW_TILES]) {
-#pragma unroll
-      for (int j = 0; j < NT_ROW_TILES; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-      const int nk = (K + TK_BK - 1) / TK_BK;
-      float4 rt[2], ru[2];
-      // K % 4 == 0: a float4 is all inside the row or all outside; an outside piece reads the row's first bytes and is zeroed
-      auto fetch = [&](int kt) {
-        const int kk = kt * TK_BK;
-        const bool ok = kk + kq4 < K;
-        const int off = ok ? kk : -kq4;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const bool okt = ok && tok_ok[i];
-          float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (okt) x = *reinterpret_cast<const float4*>(ptok[i] + off);
-          const float4 y = *reinterpret_cast<const float4*>(pusr[i] + off);
-          rt[i] = x;
-          ru[i] = make_float4(ok ? y.x : 0.f, ok ? y.y : 0.f, ok ? y.z : 0.f, ok ? y.w : 0.f);
-        }
-      };
-      auto store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          *reinterpret_cast<float4*>(&Ts[buf * TK_TILE_FLOATS + sdst[i]]) = rt[i];
-          *reinterpret_cast<float4*>(&Us[buf * TK_TILE_FLOATS + sdst[i]]) = ru[i];
-        }
-      };
-      // contraction index of MFMA step 4 j8' + w of lane half kl: k = 8 j8 + 4 kl + w, the same for both operands
-      auto mma = [&](int buf) {
-        const float* ts = Ts + buf * TK_TILE_FLOATS + il * 16;
-        const float* us = Us + buf * TK_TILE_FLOATS + (wave * 32 + il) * 16;
-        const int sw = (il >> 2) & 3;
-#pragma unroll
-        for (int j8 = 0; j8 < TK_BK / 8; ++j8) {
-          const int q = ((2 * j8 + kl) ^ sw) * 4;
-          float uv[4], tv[NT_ROW_TILES][4];
-#pragma unroll
-          for (int w = 0; w < 4; ++w) uv[w] = us[q + w];
-#pragma unroll
-          for (int j = 0; j < NT_ROW_TILES; ++j)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) tv[j][w] = ts[j * 32 * 16 + q + w];
-#pragma unroll
-          for (int w = 0; w < 4; ++w)
-#pragma unroll
-            for (int j = 0; j < NT_ROW_TILES; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(tv[j][w], uv[w], acc[j], 0, 0, 0);
-        }
-      };
-      fetch(0);
-      store(0);
-      __syncthreads();
-      for (int kt = 0; kt < nk; kt += 2) {
-        if (kt + 1 < nk) fetch(kt + 1);
-        if (wave_on) mma(0);
-        if (kt + 1 < nk) store(1);
-        __syncthreads();
-        if (kt + 1 < nk) {
-          if (kt + 2 < nk) fetch(kt + 2);
-          if (wave_on) mma(1);
-          if (kt + 2 < nk) store(0);
-          __syncthreads();
-        }
-      }
-    };
-
-    // ---- phase 1: logits, turned into e_l = exp(s_l - max) in place.  C/D map: user = lane & 31, token row of tile j =
-    // (r & 3) + 8 (r >> 2) + 4 (lane >> 5); candidate c owns tiles c LT .. c LT + LT - 1
-    f32x16 ew[NT_ROW_TILES];
-    gemm(pa, pq, A, ew);
-    float den[CPS];
-#pragma unroll
-    for (int c = 0; c < CPS; ++c) {
-      if (!wave_on) {  // wave-uniform; never true in the plain form
-        den[c] = 1.f;
-        continue;
-      }
-      float m = -INFINITY;
-#pragma unroll
-      for (int lt = 0; lt < LT; ++lt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int l = lt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl;
-          const float s = l < L ? ew[c * LT + lt][r] : -INFINITY;  // padded token: weight 0
-          ew[c * LT + lt][r] = s;
-          m = fmaxf(m, s);
-        }
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
-      float sum = 0.f;
-#pragma unroll
-      for (int lt = 0; lt < LT; ++lt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = expf(ew[c * LT + lt][r] - m);
-          ew[c * LT + lt][r] = e;
-          sum += e;
-        }
-      den[c] = sum + __shfl_xor(sum, 32, 64);
-    }
-
-    // ---- phase 2: dots, and the score (both lane halves end with the same bits: the cross-half add is commutative)
-    f32x16 dv[NT_ROW_TILES];
-    gemm(pv, pu, F, dv);
+    // WINDOWED: a wave none of whose users' windows meets the step fills the operand images and takes the barriers, nothing else:
+    // no MFMA, no expf pass, no selection
+    const bool wave_on = !WINDOWED || walk_meets(sp, n0, CPS);
+    NpaPooled<LT> p;
+    npa_pooled<LT>(a, th, Ts, Us, candrow, wave, kl, il, wave_on, p);
     if (!wave_on) continue;  // wave-uniform; the barriers of the step are all behind it, the drain has none
-    auto score = [&](const int c) {
-      float num = 0.f;
-#pragma unroll
-      for (int lt = 0; lt < LT; ++lt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) num = fmaf(ew[c * LT + lt][r], dv[c * LT + lt][r], num);
-      num = num + __shfl_xor(num, 32, 64);
-      return num / den[c];
-    };
 
     // ---- selection: lane half kl offers candidates kl, kl + 2 of the step for user il; one compare against the user's current
     // k-th best (NaN survives on purpose, it has to reach the flag), survivors compacted into the wave's queue and drained
     const int rl = wave * 32 + il;
-    const float th = thr[rl];
+    const float thv = thr[rl];
     int cnt = 0;
-    // WINDOWED: the position must lie in the user's window as well -- unless the step is inside every window of this wave's users.
-    // lo <= p < hi as ONE unsigned compare: (p - lo) < (hi - lo); 0 <= lo <= hi <= M and p < 2^31, nothing wraps
-    const bool gated = WINDOWED && !(n0 >= ilo && n0 + CPS <= ihi);
-    const unsigned wd = gated ? static_cast<unsigned>(hi - lo) : UINT32_MAX;
-    const int d0 = static_cast<int>(n0) - (gated ? lo : 0);
+    // WINDOWED: the position must lie in the user's window as well -- unless the step is inside every window of this wave's users
+    const WalkGate g = WINDOWED && walk_gated(sp, n0, CPS) ? walk_gate(lo, hi) : WalkGate();
+    const int c0 = static_cast<int>(n0);
     auto offer = [&](const float s, const int c) {
-      const bool pass = !(s < th) && (!WINDOWED || static_cast<unsigned>(d0 + c) < wd);
+      const bool pass = !(s < thv) && (!WINDOWED || g.pass(c0 + c));
       const unsigned long long m = __ballot(pass);
       if (pass) {
         const int slot = cnt + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
@@ -330,11 +128,11 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
       cnt += __popcll(m);
     };
     {
-      const float s0 = score(0), s1 = score(1);
+      const float s0 = p.score(0), s1 = p.score(1);
       offer(kl ? s1 : s0, kl);
     }
     if constexpr (CPS == 4) {
-      const float s2 = score(2), s3 = score(3);
+      const float s2 = p.score(2), s3 = p.score(3);
       offer(kl ? s3 : s2, 2 + kl);
     }
     topk_list_drain(a, lds, cnt, u0, n0, lane, saw_nan);
@@ -342,16 +140,6 @@ __global__ __launch_bounds__(TK_THREADS, 2) void npa_topk_kernel(NpaTopkArgs a) 
 
   if (saw_nan) a.flags[1] = 1;
   topk_list_write(a, lds, u0, split, wave, lane);
-}
-
-inline int npa_cands_per_step(int32_t L) { return L <= 32 ? NT_ROW_TILES : NT_ROW_TILES / 2; }
-
-int npa_resolve_splits(int64_t U, int64_t M, int32_t L, int32_t n_splits) {
-  const int64_t steps = ebn_ceil_div(M, npa_cands_per_step(L));
-  int64_t s = n_splits > 0 ? n_splits : ebn_npa_topk_auto_splits(U, M, L);
-  if (s > steps) s = steps;
-  if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
-  return static_cast<int>(s < 1 ? 1 : s);
 }
 
 template <int LT, bool WINDOWED>
@@ -373,12 +161,7 @@ int npa_launch(const NpaTopkArgs& a, int64_t user_tiles, int splits, hipStream_t
 
 extern "C" int ebn_npa_topk_auto_splits(int64_t n_users, int64_t n_cand, int32_t L) {
   if (!ebn_dim_ok(n_users, n_cand) || n_users == 0 || n_cand == 0 || L < 1 || L > NT_MAX_L) return 1;
-  // a few hundred workgroups (two per CU) when the users alone do not give them; never finer than one candidate step
-  const int64_t user_tiles = ebn_ceil_div(n_users, TK_BM), steps = ebn_ceil_div(n_cand, npa_cands_per_step(L));
-  int64_t s = ebn_ceil_div(512, user_tiles);
-  if (s > steps) s = steps;
-  if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
-  return static_cast<int>(s < 1 ? 1 : s);
+  return walk_resolve_splits(n_users, n_cand, npa_cands_per_step(L), 0);
 }
 
 namespace {
@@ -402,7 +185,7 @@ int npa_topk_score(const float* users, const float* Q, const float* Ua_all, cons
   EBN_REQUIRE(users != nullptr && Q != nullptr && Ua_all != nullptr && Vd_all != nullptr && n_rows >= 1, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(ebn_aligned16(users) && ebn_aligned16(Q) && ebn_aligned16(Ua_all) && ebn_aligned16(Vd_all), EBN_ERR_ALIGN);
   if (exclude == nullptr) X = 0;
-  const int splits = npa_resolve_splits(U, M, L, n_splits);
+  const int splits = walk_resolve_splits(U, M, npa_cands_per_step(L), n_splits);
   const int64_t user_tiles = ebn_ceil_div(U, TK_BM);
   EBN_REQUIRE(user_tiles <= EBN_DIM_MAX, EBN_ERR_UNSUPPORTED);
   NpaTopkArgs a;
@@ -426,7 +209,7 @@ int npa_topk_score(const float* users, const float* Q, const float* Ua_all, cons
   a.k = k;
   a.mode = mode;
   a.n_splits = splits;
-  a.steps_per_split = static_cast<int32_t>(ebn_ceil_div(ebn_ceil_div(M, npa_cands_per_step(L)), splits));
+  a.steps_per_split = walk_units_per_split(M, npa_cands_per_step(L), splits);
   int rc = topk_bind_workspace(a, splits, workspace, workspace_bytes);
   if (rc != EBN_OK) return rc;
   rc = L <= 32 ? npa_launch<1, WINDOWED>(a, user_tiles, splits, s) : npa_launch<2, WINDOWED>(a, user_tiles, splits, s);

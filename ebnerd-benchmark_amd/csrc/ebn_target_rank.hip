@@ -7,9 +7,9 @@
 //
 // with t = s(u, target_pos[u]): the target's index + 1 in the total order of ebn_topk_score_f32 (score descending, then position
 // ascending).  The operand staging (registers -> XOR-swizzled float4 image, 16-deep slabs, two LDS buffers, one barrier per slab)
-// and the MFMA order are those of topk_score_kernel, statement for statement: an accumulator element is the same fma chain, so
-// s(u, c) has the bits ebn_topk_score_f32 gives the pair.  A 256-thread workgroup owns 128 users and walks its range of
-// 128-candidate tiles, the four waves stacked along the users.
+// and the MFMA step are topk_score_kernel's own -- walk_run and walk_mma of ebn_catalogue_walk.h, which both kernels call: an
+// accumulator element is the same fma chain, so s(u, c) has the bits ebn_topk_score_f32 gives the pair.  A 256-thread workgroup
+// owns 128 users and walks its range of 128-candidate tiles, the four waves stacked along the users.
 //
 // Target tile.  Before the walk the workgroup needs its users' t.  It runs the slab pipeline once over a tile whose candidate
 // operand row i is the catalogue row of user i's target: the diagonal of the 128 x 128 product is t.  Wave w's diagonal lies in
@@ -35,15 +35,13 @@
 // more barrier per tile, and one ds_read_b128 per accumulator register in the epilogue.  X == 0 skips all of it.  The first
 // version compared every element against the X rows directly; DESIGN.md has both measured costs.
 //
-// WINDOWED: the tile-span logic of topk_score_kernel<true> -- the workgroup's union picks the tiles, the wave's union gates its
-// MFMAs, the wave's intersection frees a tile of the per-element window compare.
+// WINDOWED: the tile-span logic of topk_score_kernel<true>, from the same header -- the workgroup's union picks the tiles, the
+// wave's union gates its MFMAs, the wave's intersection frees a tile of the per-element window compare.
+#include "ebn_catalogue_walk.h"
 #include "ebn_topk_list.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int TR_TN = TK_BN / 32;  // MFMA tiles of a wave along the candidates
 constexpr int TR_MAX_F = 8192;
 constexpr int TR_X_LDS = 32;       // exclusion lists up to this length are staged in LDS
 
@@ -64,11 +62,11 @@ struct RankArgs {
   int32_t F, X, XP, mode, n_splits, tiles_per_split;
 };
 
-// dynamic LDS layout (floats): operand images | candrow[128] | t[128] | target position[128] | lo[128] | hi[128] | admissible[128] |
-// ahead[128] | bucket head[256] | successor[128] | excluded bits [128][4] | exclude [128][XP]
+// dynamic LDS layout (floats) behind the operand images: candrow[128] | t[128] | target position[128] | lo[128] | hi[128] |
+// admissible[128] | ahead[128] | bucket head[256] | successor[128] | excluded bits [128][4] | exclude [128][XP]
 constexpr int TR_BUCKETS = 256;
-static_assert(TR_BUCKETS == TK_THREADS && TR_TN == 4, "one bucket head per thread; four words of excluded bits per row");
-inline int64_t rank_lds_bytes(int xp_lds) { return static_cast<int64_t>(4 * TK_TILE_FLOATS + 14 * TK_BM + TK_BM * xp_lds) * 4; }
+static_assert(TR_BUCKETS == TK_THREADS && TK_TILES == 4, "one bucket head per thread; four words of excluded bits per row");
+inline int64_t rank_lds_bytes(int xp_lds) { return static_cast<int64_t>(TK_IMAGE_FLOATS + 14 * TK_BM + TK_BM * xp_lds) * 4; }
 
 __device__ __forceinline__ void rank_write(const RankArgs& a, int64_t u, int count, int ahead, float t) {
   const bool ranked = t == t;
@@ -88,40 +86,30 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
   const int F = a.F, X = a.X, XP = a.XP;
   const int64_t u0 = static_cast<int64_t>(blockIdx.x) * TK_BM;
   const int split = blockIdx.y;
-  float *As = smem, *Bs = smem + 2 * TK_TILE_FLOATS;
+  const WalkImages im = walk_images(smem);
+  float *As = im.As, *Bs = im.Bs;
   // every exchange through these is across a barrier: plain pointers, LDS loads
-  int* candrow = reinterpret_cast<int*>(smem + 4 * TK_TILE_FLOATS);
-  float* tsc = smem + 4 * TK_TILE_FLOATS + TK_BM;
-  int* tps = reinterpret_cast<int*>(smem + 4 * TK_TILE_FLOATS + 2 * TK_BM);
-  int* win_lo = reinterpret_cast<int*>(smem + 4 * TK_TILE_FLOATS + 3 * TK_BM);
+  int* candrow = reinterpret_cast<int*>(im.own);
+  float* tsc = im.own + TK_BM;
+  int* tps = reinterpret_cast<int*>(im.own + 2 * TK_BM);
+  int* win_lo = reinterpret_cast<int*>(im.own + 3 * TK_BM);
   int* win_hi = win_lo + TK_BM;
-  int* lcnt = reinterpret_cast<int*>(smem + 4 * TK_TILE_FLOATS + 5 * TK_BM);  // admissible[128] | ahead[128]
-  int* head = lcnt + 2 * TK_BM;                                           // of the buckets: a column of the tile, -1 = empty
-  int* nxt = head + TR_BUCKETS;                                           // a column's successor in its bucket
-  unsigned* exbits = reinterpret_cast<unsigned*>(nxt + TK_BN);            // bit (c & 31) of [row][c >> 5]: column c is excluded for the row
+  int* lcnt = reinterpret_cast<int*>(im.own + 5 * TK_BM);       // admissible[128] | ahead[128]
+  int* head = lcnt + 2 * TK_BM;                                 // of the buckets: a column of the tile, -1 = empty
+  int* nxt = head + TR_BUCKETS;                                 // a column's successor in its bucket
+  unsigned* exbits = reinterpret_cast<unsigned*>(nxt + TK_BN);  // bit (c & 31) of [row][c >> 5]: column c is excluded for the row
   int* exl = reinterpret_cast<int*>(exbits + 4 * TK_BM);
   const bool ex_lds = X > 0 && X <= TR_X_LDS;
 
-  // this thread's two float4 of an operand slab: item v = tid + 256 i -> tile row v / 4, k quarter v % 4
+  const WalkSlab sl = walk_slab(tid);
   const float* pa[2];
-  int sdst[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int v = tid + i * TK_THREADS, mn = v >> 2, kq = v & 3;
-    int64_t u = u0 + mn;
-    u = u < a.U ? u : a.U - 1;  // rows past the last user repeat it; their counts are never written out
-    pa[i] = a.users + u * F + kq * 4;
-    sdst[i] = (mn * 4 + (kq ^ ((mn >> 2) & 3))) * 4;
-  }
-  const int kq4 = (tid & 3) * 4;
+  for (int i = 0; i < 2; ++i) pa[i] = a.users + walk_slab_user(u0, a.U, tid, i) * F + sl.kq4;
   bool saw_nan = false;
   unsigned long long nan_mask = 0ull;
 
-  const int64_t n_tiles = (a.M + TK_BN - 1) / TK_BN;
-  int64_t t_beg = static_cast<int64_t>(split) * a.tiles_per_split;
-  int64_t t_end = t_beg + a.tiles_per_split;
-  t_end = t_end < n_tiles ? t_end : n_tiles;
-  const int nk = (F + TK_BK - 1) / TK_BK;
+  int64_t t_beg, t_end;
+  walk_span(a.M, TK_BN, split, a.tiles_per_split, t_beg, t_end);
 
   // the users' clamped ranges (not WINDOWED: [0, M); a row past the last user: [0, 0)) and the target's row of the catalogue
   if (tid < TK_BM) {
@@ -129,37 +117,14 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
     int lo = 0, hi = 0, tp = -1, trow = -1;
     if (u < a.U) {
       hi = static_cast<int>(a.M);  // M <= INT32_MAX
-      if constexpr (WINDOWED) {
-        lo = a.window[2 * u];
-        hi = a.window[2 * u + 1];
-        lo = lo > 0 ? lo : 0;
-        hi = static_cast<int64_t>(hi) < a.M ? hi : static_cast<int>(a.M);
-        if (lo >= hi) lo = hi = 0;
-      }
-      tp = a.target_pos[u];
-      if (static_cast<int64_t>(tp) >= a.M) {
-        a.flags[0] = 1;
-        tp = -1;
-      }
-      if (tp < lo || tp >= hi) tp = -1;  // also tp < 0
-      if (tp >= 0) {
-        const int64_t r = a.cand_rows != nullptr ? static_cast<int64_t>(a.cand_rows[tp]) : tp;
-        if (r < 0 || r >= a.n_rows) {
-          a.flags[0] = 1;  // a row outside the table inside this user's window
-          tp = -1;
-        } else {
-          trow = static_cast<int>(r);
-          const int32_t* ex = a.exclude + u * X;
-          bool hit = false;
-          for (int x = 0; x < X; ++x) hit |= ex[x] == trow;
-          if (hit) tp = -1;
-        }
-      }
+      if constexpr (WINDOWED) walk_clamp(a.window, u, a.M, lo, hi);
+      trow = walk_target_row(a, u, lo, hi);
+      if (trow >= 0) tp = a.target_pos[u];
     }
     win_lo[tid] = lo;
     win_hi[tid] = hi;
     tps[tid] = tp;
-    candrow[tid] = tp >= 0 ? trow : -1;
+    candrow[tid] = trow;
     lcnt[tid] = 0;
     lcnt[TK_BM + tid] = 0;
   }
@@ -172,103 +137,20 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
   }
   __syncthreads();
 
-  // WINDOWED: the union of the workgroup [wlo, whi) and of this wave [vlo, vhi) over the non-empty ranges, the intersection of this
-  // wave [ilo, ihi) over its users below U.  All of them are wave-uniform.
-  int wlo = 0, whi = 0, vlo = 0, vhi = 0, ilo = 0, ihi = 0;
+  // WINDOWED: the workgroup's union picks the tiles
+  WalkSpans sp;
   if constexpr (WINDOWED) {
-    // lane l: rows l and l + 64 for the workgroup, row 32 wave + (l & 31) for the wave
-    int ulo = INT32_MAX, uhi = 0, xlo = INT32_MAX, xhi = 0, nlo = 0, nhi = INT32_MAX;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int lo = win_lo[lane + 64 * i], hi = win_hi[lane + 64 * i];
-      if (lo < hi) {
-        ulo = lo < ulo ? lo : ulo;
-        uhi = hi > uhi ? hi : uhi;
-      }
-    }
-    {
-      const int row = wave * 32 + il;
-      const int lo = win_lo[row], hi = win_hi[row];
-      if (lo < hi) {
-        xlo = lo;
-        xhi = hi;
-      }
-      if (u0 + row < a.U) {
-        nlo = lo;
-        nhi = hi;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o0 = __shfl_xor(ulo, off, 64), o1 = __shfl_xor(uhi, off, 64), o2 = __shfl_xor(xlo, off, 64);
-      const int o3 = __shfl_xor(xhi, off, 64), o4 = __shfl_xor(nlo, off, 64), o5 = __shfl_xor(nhi, off, 64);
-      ulo = o0 < ulo ? o0 : ulo;
-      uhi = o1 > uhi ? o1 : uhi;
-      xlo = o2 < xlo ? o2 : xlo;
-      xhi = o3 > xhi ? o3 : xhi;
-      nlo = o4 > nlo ? o4 : nlo;
-      nhi = o5 < nhi ? o5 : nhi;
-    }
-    wlo = __builtin_amdgcn_readfirstlane(ulo);
-    whi = __builtin_amdgcn_readfirstlane(uhi);
-    vlo = __builtin_amdgcn_readfirstlane(xlo);
-    vhi = __builtin_amdgcn_readfirstlane(xhi);
-    ilo = __builtin_amdgcn_readfirstlane(nlo);
-    ihi = __builtin_amdgcn_readfirstlane(nhi);
-    // the tiles that meet the union (none: wlo = INT32_MAX, whi = 0), dealt evenly over the splits
-    const int64_t w_beg = wlo / TK_BN, w_end = wlo < whi ? (static_cast<int64_t>(whi) + TK_BN - 1) / TK_BN : w_beg;
-    const int64_t w_n = w_end - w_beg;
-    t_beg = w_beg + w_n * split / a.n_splits;
-    t_end = w_beg + w_n * (split + 1) / a.n_splits;
+    sp = walk_spans_table(win_lo, win_hi, u0, a.U, wave, lane);
+    walk_span(sp, TK_BN, split, a.n_splits, t_beg, t_end);
   }
 
-  const float* pb[2];
-  float4 ra[2], rb[2];
-  // F % 4 == 0: a float4 is all inside the row or all outside; an outside piece reads the row's first bytes and is zeroed
-  auto fetch = [&](int kt) {
-    const int kk = kt * TK_BK;
-    const bool ok = kk + kq4 < F;
-    const int off = ok ? kk : -kq4;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float4 x = *reinterpret_cast<const float4*>(pa[i] + off);
-      const float4 y = *reinterpret_cast<const float4*>(pb[i] + off);
-      ra[i] = make_float4(ok ? x.x : 0.f, ok ? x.y : 0.f, ok ? x.z : 0.f, ok ? x.w : 0.f);
-      rb[i] = make_float4(ok ? y.x : 0.f, ok ? y.y : 0.f, ok ? y.z : 0.f, ok ? y.w : 0.f);
-    }
-  };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      *reinterpret_cast<float4*>(&As[buf * TK_TILE_FLOATS + sdst[i]]) = ra[i];
-      *reinterpret_cast<float4*>(&Bs[buf * TK_TILE_FLOATS + sdst[i]]) = rb[i];
-    }
-  };
   // the candidate operand rows of the tile whose catalogue rows candrow[] holds (behind a barrier)
+  const float* pb[2];
   auto point_b = [&]() {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int mn = (tid + i * TK_THREADS) >> 2;
-      const int r = candrow[mn];
-      pb[i] = a.news + static_cast<int64_t>(r > 0 ? r : 0) * F + kq4;
-    }
-  };
-  // the slab pipeline of one tile; mma(buf) only when this wave has something to compute
-  auto run_tile = [&](bool wave_on, auto&& mma) {
-    fetch(0);
-    store(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt += 2) {
-      if (kt + 1 < nk) fetch(kt + 1);
-      if (wave_on) mma(0);
-      if (kt + 1 < nk) store(1);
-      __syncthreads();
-      if (kt + 1 < nk) {
-        if (kt + 2 < nk) fetch(kt + 2);
-        if (wave_on) mma(1);
-        if (kt + 2 < nk) store(0);
-        __syncthreads();
-      }
+      const int r = candrow[walk_slab_row(tid, i)];
+      pb[i] = a.news + static_cast<int64_t>(r > 0 ? r : 0) * F + sl.kq4;
     }
   };
 
@@ -278,14 +160,12 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
     f32x16 acc_t;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc_t[r] = 0.f;
-    // contraction index of MFMA step 4 j8' + w of lane half kl: k = 8 j8 + 4 kl + w, the same for both operands
     auto mma_diag = [&](int buf) {
       const float* as = As + buf * TK_TILE_FLOATS + (wave * 32 + il) * 16;
       const float* bs = Bs + buf * TK_TILE_FLOATS + (wave * 32 + il) * 16;
-      const int sw = (il >> 2) & 3;
 #pragma unroll
       for (int j8 = 0; j8 < TK_BK / 8; ++j8) {
-        const int q = ((2 * j8 + kl) ^ sw) * 4;
+        const int q = walk_quad(j8, kl, il);
         float av[4], bv[4];
 #pragma unroll
         for (int w = 0; w < 4; ++w) av[w] = as[q + w];
@@ -295,7 +175,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
         for (int w = 0; w < 4; ++w) acc_t = __builtin_amdgcn_mfma_f32_32x32x2f32(av[w], bv[w], acc_t, 0, 0, 0);
       }
     };
-    run_tile(true, mma_diag);
+    walk_run(As, Bs, sl, pa, pb, nullptr, F, true, mma_diag);
     // C/D map of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int r = 0; r < 16; ++r)
@@ -317,20 +197,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
   for (int64_t t = t_beg; t < t_end; ++t) {
     const int64_t n0 = t * TK_BN;
     __syncthreads();  // every wave is done with the previous tile's candrow
-    if (tid < TK_BN) {
-      const int64_t c = n0 + tid;
-      int row = -2;  // past the last candidate
-      if (c < a.M) {
-        const int64_t r = a.cand_rows != nullptr ? static_cast<int64_t>(a.cand_rows[c]) : c;
-        if (r < 0 || r >= a.n_rows) {
-          row = -1;  // never turned into an address
-          if (!WINDOWED || (c >= wlo && c < whi)) a.flags[0] = 1;  // a visited tile also has columns outside the union
-        } else {
-          row = static_cast<int>(r);
-        }
-      }
-      candrow[tid] = row;
-    }
+    walk_rows<WINDOWED>(a, sp, n0, TK_BN, tid, candrow);
     if (X > 0) {
       head[tid] = -1;  // TR_BUCKETS == TK_THREADS
       exbits[tid] = 0u;
@@ -358,61 +225,30 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
       }
     }
 
-    f32x16 acc[TR_TN];
-#pragma unroll
-    for (int j = 0; j < TR_TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-    auto mma = [&](int buf) {
-      const float* as = As + buf * TK_TILE_FLOATS + (wave * 32 + il) * 16;
-      const float* bs = Bs + buf * TK_TILE_FLOATS + il * 16;
-      const int sw = (il >> 2) & 3;
-#pragma unroll
-      for (int j8 = 0; j8 < TK_BK / 8; ++j8) {
-        const int q = ((2 * j8 + kl) ^ sw) * 4;
-        float av[4], bv[TR_TN][4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) av[w] = as[q + w];
-#pragma unroll
-        for (int j = 0; j < TR_TN; ++j)
-#pragma unroll
-          for (int w = 0; w < 4; ++w) bv[j][w] = bs[j * 32 * 16 + q + w];
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-#pragma unroll
-          for (int j = 0; j < TR_TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[w], bv[j][w], acc[j], 0, 0, 0);
-      }
-    };
-
     // WINDOWED: a wave none of whose users' windows meets the tile fills the operand images and takes the barriers, nothing else
-    const bool wave_on = !WINDOWED || (n0 < vhi && n0 + TK_BN > vlo);
-    run_tile(wave_on, mma);
+    const bool wave_on = !WINDOWED || walk_meets(sp, n0, TK_BN);
+    f32x16 acc[TK_TILES];
+    walk_zero(acc);
+    walk_run(As, Bs, sl, pa, pb, nullptr, F, wave_on, [&](int buf) { walk_mma<true>(As, Bs, buf, wave, kl, il, acc); });
     if (!wave_on) continue;
 
     // ---- counting.  Column = lane & 31 of MFMA tile j, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     // WINDOWED: the column must lie in the row's window as well -- unless the tile is inside every window of this wave's users
-    const bool gated = WINDOWED && !(n0 >= ilo && n0 + TK_BN <= ihi);
+    const bool gated = WINDOWED && walk_gated(sp, n0, TK_BN);
     const int c0 = static_cast<int>(n0) + il;  // this lane's column of MFMA tile 0
-    int crow[TR_TN];
+    int crow[TK_TILES];
 #pragma unroll
-    for (int j = 0; j < TR_TN; ++j) crow[j] = candrow[32 * j + il];
+    for (int j = 0; j < TK_TILES; ++j) crow[j] = candrow[32 * j + il];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int rl = rbase + (r & 3) + 8 * (r >> 2);
       const float tt = tsc[rl];
       const int tp = tps[rl];
-      // lo <= c < hi as ONE unsigned compare: (c - lo) < (hi - lo); 0 <= lo <= hi <= M and c < 2^31, nothing wraps
-      int d = 0;
-      unsigned w = UINT32_MAX;
+      WalkGate g;
       if constexpr (WINDOWED) {
-        if (gated) {
-          const int lo = win_lo[rl];
-          d = c0 - lo;
-          w = static_cast<unsigned>(win_hi[rl] - lo);
-        }
+        if (gated) g = walk_gate(win_lo[rl], win_hi[rl]);
       }
-      bool hit[TR_TN];
+      bool hit[TK_TILES];
       {
         uint4 xb = make_uint4(0u, 0u, 0u, 0u);
         if (X > 0) xb = *reinterpret_cast<const uint4*>(&exbits[rl * 4]);
@@ -423,9 +259,9 @@ __global__ __launch_bounds__(TK_THREADS, 2) void target_rank_kernel(RankArgs a) 
       }
       int n_adm[2] = {0, 0}, n_ahd[2] = {0, 0};  // of the rows of lane half 0 and 1: wave-uniform
 #pragma unroll
-      for (int j = 0; j < TR_TN; ++j) {
+      for (int j = 0; j < TK_TILES; ++j) {
         const float s = acc[j][r];
-        const bool inside = crow[j] >= 0 && (!WINDOWED || static_cast<unsigned>(d + 32 * j) < w);
+        const bool inside = crow[j] >= 0 && (!WINDOWED || g.pass(c0 + 32 * j));
         nan_mask |= __ballot(inside && s != s);
         const bool adm = inside && s == s && !hit[j];
         const unsigned long long m_adm = __ballot(adm);
@@ -482,14 +318,6 @@ __global__ __launch_bounds__(256) void target_rank_empty_kernel(const int32_t* _
   }
 }
 
-int rank_resolve_splits(int64_t U, int64_t M, int32_t n_splits) {
-  const int64_t tiles = ebn_ceil_div(M, TK_BN);
-  int64_t s = n_splits > 0 ? n_splits : ebn_topk_auto_splits(U, M);
-  if (s > tiles) s = tiles;
-  if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
-  return static_cast<int>(s < 1 ? 1 : s);
-}
-
 }  // namespace
 
 extern "C" int64_t ebn_target_rank_workspace_bytes(int64_t n_users, int32_t n_splits) {
@@ -522,7 +350,7 @@ extern "C" int ebn_target_rank_f32(const float* users, const float* news_all, in
   EBN_REQUIRE(users != nullptr && news_all != nullptr && n_rows >= 1, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(ebn_aligned16(users) && ebn_aligned16(news_all), EBN_ERR_ALIGN);
   if (exclude == nullptr) X = 0;
-  const int splits = rank_resolve_splits(U, M, n_splits);
+  const int splits = walk_resolve_splits(U, M, TK_BN, n_splits);
   const int64_t user_tiles = ebn_ceil_div(U, TK_BM);
   EBN_REQUIRE(user_tiles <= EBN_DIM_MAX, EBN_ERR_UNSUPPORTED);
   RankArgs a;
@@ -546,7 +374,7 @@ extern "C" int ebn_target_rank_f32(const float* users, const float* news_all, in
   a.XP = (X + 3) / 4 * 4;
   a.mode = mode;
   a.n_splits = splits;
-  a.tiles_per_split = static_cast<int32_t>(ebn_ceil_div(ebn_ceil_div(M, TK_BN), splits));
+  a.tiles_per_split = walk_units_per_split(M, TK_BN, splits);
   if (splits > 1) {
     const int64_t need = ebn_target_rank_workspace_bytes(U, splits);
     EBN_REQUIRE(workspace != nullptr && workspace_bytes >= need, EBN_ERR_BAD_ARG);

@@ -21,6 +21,8 @@
 // the split, partial lists are merged in the same order by a second launch.  Bit-identical for every n_splits and from run to run.
 // Ranking is on the raw dot product; the sigmoid is applied to the k kept values when they are written.
 // The list code (LDS plan, drain and insert, write-out, merge and fill launches) is ebn_topk_list.h, shared with ebn_npa_topk.hip.
+// Everything ahead of the selection -- operand staging, the MFMA step, the window reductions and tile spans, the tile's catalogue
+// rows -- is ebn_catalogue_walk.h, shared with ebn_target_rank.hip and the two NPA kernels: this file is the epilogue.
 //
 // Windowed form (ebn_topk_score_window_f32, the WINDOWED instantiation): user u may only receive the candidate positions of
 // window[u] = [lo, hi), clamped to [0, M).  The workgroup keeps its 128 users' clamped ranges in LDS behind the list plan (1 KB),
@@ -30,13 +32,11 @@
 // barriers; an accumulator element is a survivor only when its column also lies in its row's window (a tile inside every window of
 // the wave takes the plain compare), so nothing outside a window reaches the queue, the NaN flag or the lists.  A pair's dot
 // product is the same fma chain as in the plain form: the same bits, whatever the windows, the split and the other users are.
+#include "ebn_catalogue_walk.h"
 #include "ebn_topk_list.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int TK_TN = TK_BN / 32;      // MFMA tiles of a wave along the candidates
 constexpr int TK_MAX_F = 8192;
 static_assert(TK_QCAP >= 2 * TK_BN, "the survivors of one accumulator index: 2 rows x 128 columns");
 
@@ -73,209 +73,71 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
   topk_list_init(lds, k, tid);
   __syncthreads();  // a range without tiles (more splits than tiles divide into) still writes its empty lists out
 
-  // this thread's two float4 of an operand slab: item v = tid + 256 i -> tile row v / 4, k quarter v % 4
+  const WalkSlab sl = walk_slab(tid);
   const float* pa[2];
-  int sdst[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int v = tid + i * TK_THREADS, mn = v >> 2, kq = v & 3;
-    int64_t u = u0 + mn;
-    u = u < a.U ? u : a.U - 1;  // rows past the last user repeat it; their lists are never written out
-    pa[i] = a.users + u * F + kq * 4;
-    sdst[i] = (mn * 4 + (kq ^ ((mn >> 2) & 3))) * 4;
-  }
-  const int kq4 = (tid & 3) * 4;
+  for (int i = 0; i < 2; ++i) pa[i] = a.users + walk_slab_user(u0, a.U, tid, i) * F + sl.kq4;
   bool saw_nan = false;
 
-  const int64_t n_tiles = (a.M + TK_BN - 1) / TK_BN;
-  int64_t t_beg = static_cast<int64_t>(split) * a.tiles_per_split;
-  int64_t t_end = t_beg + a.tiles_per_split;
-  t_end = t_end < n_tiles ? t_end : n_tiles;
-  const int nk = (F + TK_BK - 1) / TK_BK;
+  int64_t t_beg, t_end;
+  walk_span(a.M, TK_BN, split, a.tiles_per_split, t_beg, t_end);
 
-  // WINDOWED: the users' clamped ranges (an empty one, and a row past the last user, is [0, 0): no column passes), the union of
-  // the workgroup [wlo, whi) and of this wave [vlo, vhi) over the non-empty ones, the intersection of this wave [ilo, ihi) over
-  // its users below U.  All of them are wave-uniform.
+  // WINDOWED: the users' clamped ranges in LDS (a row past the last user is [0, 0)); the workgroup's union picks the tiles
   volatile int* win_lo = lds.lps + TK_BM * k;  // the end of the plan: topk_lds_bytes(k)
   volatile int* win_hi = win_lo + TK_BM;
-  int wlo = 0, whi = 0, vlo = 0, vhi = 0, ilo = 0, ihi = 0;
+  WalkSpans sp;
   if constexpr (WINDOWED) {
     if (tid < TK_BM) {
       const int64_t u = u0 + tid;
       int lo = 0, hi = 0;
-      if (u < a.U) {
-        lo = a.window[2 * u];
-        hi = a.window[2 * u + 1];
-        lo = lo > 0 ? lo : 0;
-        hi = static_cast<int64_t>(hi) < a.M ? hi : static_cast<int>(a.M);  // M <= INT32_MAX
-        if (lo >= hi) lo = hi = 0;
-      }
+      if (u < a.U) walk_clamp(a.window, u, a.M, lo, hi);
       win_lo[tid] = lo;
       win_hi[tid] = hi;
     }
     __syncthreads();
-    // lane l: rows l and l + 64 for the workgroup, row 32 wave + (l & 31) for the wave
-    int ulo = INT32_MAX, uhi = 0, xlo = INT32_MAX, xhi = 0, nlo = 0, nhi = INT32_MAX;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int lo = win_lo[lane + 64 * i], hi = win_hi[lane + 64 * i];
-      if (lo < hi) {
-        ulo = lo < ulo ? lo : ulo;
-        uhi = hi > uhi ? hi : uhi;
-      }
-    }
-    {
-      const int row = wave * 32 + il;
-      const int lo = win_lo[row], hi = win_hi[row];
-      if (lo < hi) {
-        xlo = lo;
-        xhi = hi;
-      }
-      if (u0 + row < a.U) {
-        nlo = lo;
-        nhi = hi;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o0 = __shfl_xor(ulo, off, 64), o1 = __shfl_xor(uhi, off, 64), o2 = __shfl_xor(xlo, off, 64);
-      const int o3 = __shfl_xor(xhi, off, 64), o4 = __shfl_xor(nlo, off, 64), o5 = __shfl_xor(nhi, off, 64);
-      ulo = o0 < ulo ? o0 : ulo;
-      uhi = o1 > uhi ? o1 : uhi;
-      xlo = o2 < xlo ? o2 : xlo;
-      xhi = o3 > xhi ? o3 : xhi;
-      nlo = o4 > nlo ? o4 : nlo;
-      nhi = o5 < nhi ? o5 : nhi;
-    }
-    wlo = __builtin_amdgcn_readfirstlane(ulo);
-    whi = __builtin_amdgcn_readfirstlane(uhi);
-    vlo = __builtin_amdgcn_readfirstlane(xlo);
-    vhi = __builtin_amdgcn_readfirstlane(xhi);
-    ilo = __builtin_amdgcn_readfirstlane(nlo);
-    ihi = __builtin_amdgcn_readfirstlane(nhi);
-    // the tiles that meet the union (none: wlo = INT32_MAX, whi = 0), dealt evenly over the splits
-    const int64_t w_beg = wlo / TK_BN, w_end = wlo < whi ? (static_cast<int64_t>(whi) + TK_BN - 1) / TK_BN : w_beg;
-    const int64_t w_n = w_end - w_beg;
-    t_beg = w_beg + w_n * split / a.n_splits;
-    t_end = w_beg + w_n * (split + 1) / a.n_splits;
+    sp = walk_spans_table(win_lo, win_hi, u0, a.U, wave, lane);
+    walk_span(sp, TK_BN, split, a.n_splits, t_beg, t_end);
   }
 
   for (int64_t t = t_beg; t < t_end; ++t) {
     const int64_t n0 = t * TK_BN;
     __syncthreads();  // every wave is done with the previous tile's candrow (and the lists are initialised)
-    if (tid < TK_BN) {
-      const int64_t c = n0 + tid;
-      int row = -2;  // past the last candidate
-      if (c < a.M) {
-        const int64_t r = a.cand_rows != nullptr ? static_cast<int64_t>(a.cand_rows[c]) : c;
-        if (r < 0 || r >= a.n_rows) {
-          row = -1;  // never turned into an address
-          if (!WINDOWED || (c >= wlo && c < whi)) a.flags[0] = 1;  // a visited tile also has columns outside the union
-        } else {
-          row = static_cast<int>(r);
-        }
-      }
-      candrow[tid] = row;
-    }
+    walk_rows<WINDOWED>(a, sp, n0, TK_BN, tid, candrow);
     __syncthreads();
     const float* pb[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int mn = (tid + i * TK_THREADS) >> 2;
-      const int r = candrow[mn];
-      pb[i] = a.news + static_cast<int64_t>(r > 0 ? r : 0) * F + kq4;
+      const int r = candrow[walk_slab_row(tid, i)];
+      pb[i] = a.news + static_cast<int64_t>(r > 0 ? r : 0) * F + sl.kq4;
     }
-
-    f32x16 acc[TK_TN];
-#pragma unroll
-    for (int j = 0; j < TK_TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-    float4 ra[2], rb[2];
-    // F % 4 == 0: a float4 is all inside the row or all outside; an outside piece reads the row's first bytes and is zeroed
-    auto fetch = [&](int kt) {
-      const int kk = kt * TK_BK;
-      const bool ok = kk + kq4 < F;
-      const int off = ok ? kk : -kq4;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float4 x = *reinterpret_cast<const float4*>(pa[i] + off);
-        const float4 y = *reinterpret_cast<const float4*>(pb[i] + off);
-        ra[i] = make_float4(ok ? x.x : 0.f, ok ? x.y : 0.f, ok ? x.z : 0.f, ok ? x.w : 0.f);
-        rb[i] = make_float4(ok ? y.x : 0.f, ok ? y.y : 0.f, ok ? y.z : 0.f, ok ? y.w : 0.f);
-      }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        *reinterpret_cast<float4*>(&As[buf * TK_TILE_FLOATS + sdst[i]]) = ra[i];
-        *reinterpret_cast<float4*>(&Bs[buf * TK_TILE_FLOATS + sdst[i]]) = rb[i];
-      }
-    };
-    // contraction index of MFMA step 4 j8' + w of lane half kl: k = 8 j8 + 4 kl + w, the same for both operands
-    auto mma = [&](int buf) {
-      const float* as = As + buf * TK_TILE_FLOATS + (wave * 32 + il) * 16;
-      const float* bs = Bs + buf * TK_TILE_FLOATS + il * 16;
-      const int sw = (il >> 2) & 3;
-#pragma unroll
-      for (int j8 = 0; j8 < TK_BK / 8; ++j8) {
-        const int q = ((2 * j8 + kl) ^ sw) * 4;
-        float av[4], bv[TK_TN][4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) av[w] = as[q + w];
-#pragma unroll
-        for (int j = 0; j < TK_TN; ++j)
-#pragma unroll
-          for (int w = 0; w < 4; ++w) bv[j][w] = bs[j * 32 * 16 + q + w];
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-#pragma unroll
-          for (int j = 0; j < TK_TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[w], bv[j][w], acc[j], 0, 0, 0);
-      }
-    };
 
     // WINDOWED: a wave none of whose users' windows meets the tile fills the operand images and takes the barriers, nothing else
-    const bool wave_on = !WINDOWED || (n0 < vhi && n0 + TK_BN > vlo);
-    fetch(0);
-    store(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt += 2) {
-      if (kt + 1 < nk) fetch(kt + 1);
-      if (wave_on) mma(0);
-      if (kt + 1 < nk) store(1);
-      __syncthreads();
-      if (kt + 1 < nk) {
-        if (kt + 2 < nk) fetch(kt + 2);
-        if (wave_on) mma(1);
-        if (kt + 2 < nk) store(0);
-        __syncthreads();
-      }
-    }
+    const bool wave_on = !WINDOWED || walk_meets(sp, n0, TK_BN);
+    f32x16 acc[TK_TILES];
+    walk_zero(acc);
+    walk_run(As, Bs, sl, pa, pb, nullptr, F, wave_on, [&](int buf) { walk_mma<true>(As, Bs, buf, wave, kl, il, acc); });
     if (!wave_on) continue;
 
     // ---- selection.  C/D map of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const int rbase = wave * 32 + 4 * kl;
     // WINDOWED: the column must lie in the row's window as well -- unless the tile is inside every window of this wave's users
-    const bool gated = WINDOWED && !(n0 >= ilo && n0 + TK_BN <= ihi);
+    const bool gated = WINDOWED && walk_gated(sp, n0, TK_BN);
     const int c0 = static_cast<int>(n0) + il;  // this lane's column of MFMA tile 0
+    auto row_gate = [&](int rl) {
+      WalkGate g;
+      if constexpr (WINDOWED) {
+        if (gated) g = walk_gate(win_lo[rl], win_hi[rl]);
+      }
+      return g;
+    };
     bool any = false;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int rl = rbase + (r & 3) + 8 * (r >> 2);
       const float th = thr[rl];
-      // lo <= c < hi as ONE unsigned compare: (c - lo) < (hi - lo); 0 <= lo <= hi <= M and c < 2^31, nothing wraps
-      int d = 0;
-      unsigned w = UINT32_MAX;
-      if constexpr (WINDOWED) {
-        if (gated) {
-          const int lo = win_lo[rl];
-          d = c0 - lo;
-          w = static_cast<unsigned>(win_hi[rl] - lo);
-        }
-      }
+      const WalkGate g = row_gate(rl);
 #pragma unroll
-      for (int j = 0; j < TK_TN; ++j) any |= !(acc[j][r] < th) && (!WINDOWED || static_cast<unsigned>(d + 32 * j) < w);
+      for (int j = 0; j < TK_TILES; ++j) any |= !(acc[j][r] < th) && (!WINDOWED || g.pass(c0 + 32 * j));
     }
     if (__ballot(any) == 0ull) continue;
 
@@ -283,19 +145,11 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
     for (int r = 0; r < 16; ++r) {
       const int rl = rbase + (r & 3) + 8 * (r >> 2);
       const float th = thr[rl];
-      int d = 0;
-      unsigned w = UINT32_MAX;
-      if constexpr (WINDOWED) {
-        if (gated) {
-          const int lo = win_lo[rl];
-          d = c0 - lo;
-          w = static_cast<unsigned>(win_hi[rl] - lo);
-        }
-      }
+      const WalkGate g = row_gate(rl);
       int cnt = 0;
 #pragma unroll
-      for (int j = 0; j < TK_TN; ++j) {
-        const bool pass = !(acc[j][r] < th) && (!WINDOWED || static_cast<unsigned>(d + 32 * j) < w);
+      for (int j = 0; j < TK_TILES; ++j) {
+        const bool pass = !(acc[j][r] < th) && (!WINDOWED || g.pass(c0 + 32 * j));
         const unsigned long long m = __ballot(pass);
         if (pass) {
           const int slot = cnt + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
@@ -312,24 +166,11 @@ __global__ __launch_bounds__(TK_THREADS, 2) void topk_score_kernel(TopkArgs a) {
   topk_list_write(a, lds, u0, split, wave, lane);
 }
 
-int topk_resolve_splits(int64_t U, int64_t M, int32_t n_splits) {
-  const int64_t tiles = ebn_ceil_div(M, TK_BN);
-  int64_t s = n_splits > 0 ? n_splits : ebn_topk_auto_splits(U, M);
-  if (s > tiles) s = tiles;
-  if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
-  return static_cast<int>(s < 1 ? 1 : s);
-}
-
 }  // namespace
 
 extern "C" int ebn_topk_auto_splits(int64_t n_users, int64_t n_cand) {
   if (!ebn_dim_ok(n_users, n_cand) || n_users == 0 || n_cand == 0) return 1;
-  // a few hundred workgroups (two per CU) when the users alone do not give them; never finer than one candidate tile
-  const int64_t user_tiles = ebn_ceil_div(n_users, TK_BM), tiles = ebn_ceil_div(n_cand, TK_BN);
-  int64_t s = ebn_ceil_div(512, user_tiles);
-  if (s > tiles) s = tiles;
-  if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
-  return static_cast<int>(s < 1 ? 1 : s);
+  return walk_resolve_splits(n_users, n_cand, TK_BN, 0);
 }
 
 extern "C" int64_t ebn_topk_workspace_bytes(int64_t n_users, int32_t k, int32_t n_splits) {
@@ -358,7 +199,7 @@ int topk_score(const float* users, const float* news_all, int64_t n_rows, const 
   EBN_REQUIRE(users != nullptr && news_all != nullptr && n_rows >= 1, EBN_ERR_BAD_ARG);
   EBN_REQUIRE(ebn_aligned16(users) && ebn_aligned16(news_all), EBN_ERR_ALIGN);
   if (exclude == nullptr) X = 0;
-  const int splits = topk_resolve_splits(U, M, n_splits);
+  const int splits = walk_resolve_splits(U, M, TK_BN, n_splits);
   const int64_t user_tiles = ebn_ceil_div(U, TK_BM);
   EBN_REQUIRE(user_tiles <= EBN_DIM_MAX, EBN_ERR_UNSUPPORTED);
   TopkArgs a;
@@ -378,7 +219,7 @@ int topk_score(const float* users, const float* news_all, int64_t n_rows, const 
   a.k = k;
   a.mode = mode;
   a.n_splits = splits;
-  a.tiles_per_split = static_cast<int32_t>(ebn_ceil_div(ebn_ceil_div(M, TK_BN), splits));
+  a.tiles_per_split = walk_units_per_split(M, TK_BN, splits);
   const int rc = topk_bind_workspace(a, splits, workspace, workspace_bytes);
   if (rc != EBN_OK) return rc;
   constexpr int extra = WINDOWED ? TK_WINDOW_LDS_BYTES : 0;

@@ -6,17 +6,13 @@
 // The order is total -- score descending, then candidate position ascending -- so a list does not depend on the order in which
 // survivors arrive, nor on how the candidates are split over workgroups; partial lists are merged in the same order.
 #pragma once
-#include <math.h>
-
-#include "ebn_common.h"
+#include "ebn_catalogue_walk.h"
 
 namespace {
 
-constexpr int TK_BM = 128, TK_BN = 128, TK_BK = 16, TK_THREADS = 256;
 constexpr int TK_QCAP = 2 * TK_BN;     // capacity of a wave's survivor queue
-constexpr int TK_MAX_K = 64, TK_MAX_X = 256, TK_MAX_SPLITS = 64;
+constexpr int TK_MAX_K = 64, TK_MAX_X = 256;
 constexpr int TK_EMPTY = INT32_MAX;    // position of an empty slot inside the kernels (sorts after every real candidate)
-constexpr int TK_TILE_FLOATS = TK_BM * TK_BK;  // one operand slab image
 
 // what the list code needs of a call; the scoring kernels' argument blocks derive from it
 struct TopkList {
@@ -35,8 +31,8 @@ __device__ __forceinline__ float topk_act(float s, int mode) { return mode == 1 
 // (s0, p0) ranks strictly before (s1, p1)
 __device__ __forceinline__ bool topk_before(float s0, int p0, float s1, int p1) { return s0 > s1 || (s0 == s1 && p0 < p1); }
 
-// dynamic LDS layout (floats): operand images | thr[128] | candrow[128] | queue score[4][256] | queue rowcol[4][256] | list score
-// [128][k] | list pos [128][k]
+// dynamic LDS layout (floats) behind the operand images: thr[128] | candrow[128] | queue score[4][256] | queue rowcol[4][256] | list
+// score [128][k] | list pos [128][k]
 struct TopkLds {
   float *As, *Bs;  // 2 buffers each
   volatile float* thr;
@@ -48,20 +44,21 @@ struct TopkLds {
 };
 
 __device__ __forceinline__ TopkLds topk_lds(float* smem, int wave, int k) {
+  const WalkImages im = walk_images(smem);
   TopkLds l;
-  l.As = smem;
-  l.Bs = smem + 2 * TK_TILE_FLOATS;
-  l.thr = smem + 4 * TK_TILE_FLOATS;
-  l.candrow = reinterpret_cast<volatile int*>(smem + 4 * TK_TILE_FLOATS + TK_BM);
-  l.qs = smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN + wave * TK_QCAP;
-  l.qrc = reinterpret_cast<volatile int*>(smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN + 4 * TK_QCAP) + wave * TK_QCAP;
-  l.lsc = smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN + 8 * TK_QCAP;
-  l.lps = reinterpret_cast<volatile int*>(smem + 4 * TK_TILE_FLOATS + TK_BM + TK_BN + 8 * TK_QCAP + TK_BM * k);
+  l.As = im.As;
+  l.Bs = im.Bs;
+  l.thr = im.own;
+  l.candrow = reinterpret_cast<volatile int*>(im.own + TK_BM);
+  l.qs = im.own + TK_BM + TK_BN + wave * TK_QCAP;
+  l.qrc = reinterpret_cast<volatile int*>(im.own + TK_BM + TK_BN + 4 * TK_QCAP) + wave * TK_QCAP;
+  l.lsc = im.own + TK_BM + TK_BN + 8 * TK_QCAP;
+  l.lps = reinterpret_cast<volatile int*>(im.own + TK_BM + TK_BN + 8 * TK_QCAP + TK_BM * k);
   return l;
 }
 
 inline int64_t topk_lds_bytes(int k) {
-  return static_cast<int64_t>(4 * TK_TILE_FLOATS + TK_BM + TK_BN + 8 * TK_QCAP + 2 * TK_BM * k) * 4;
+  return static_cast<int64_t>(TK_IMAGE_FLOATS + TK_BM + TK_BN + 8 * TK_QCAP + 2 * TK_BM * k) * 4;
 }
 
 // empty lists; the caller's next __syncthreads() publishes them

@@ -29,7 +29,7 @@ for p in (str(ROOT), str(ROOT / "ebnerd-benchmark_amd")):
 from ebrec import _hip  # noqa: E402
 from ebrec.models.newsrec._recommend import topk, topk_window  # noqa: E402
 
-TILE = 128  # users per workgroup and candidates per tile (csrc/ebn_topk_list.h)
+TILE = 128  # users per workgroup and candidates per tile (csrc/ebn_catalogue_walk.h)
 
 
 def timed(fn):
