@@ -2,6 +2,9 @@ from .content import (  # noqa: F401
     ContentSimilarity, content_centroid_scores_host, content_nearest_scores_host, content_profiles_host, history_weight_values,
     unit_rows_host,
 )
+from .covisit import (  # noqa: F401
+    CoVisitation, CoVisitMatrix, covisit_matrix_host, covisit_pair_keys_host, covisit_scores_host, covisit_values_host,
+)
 from .popularity import (  # noqa: F401
     ArticleFeatureBaseline, InviewEstimateBaseline, PopularityIndex, RecentPopularity, WindowCounts, lexicographic_scores,
     window_counts_host,

@@ -1406,6 +1406,51 @@ int ebn_cs_nearest_scores_f32(const float* table, int64_t n_rows, int64_t D, int
                               const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets, int64_t n_lists,
                               int64_t n_cand_items, float* scores, ebn_stream_t stream);
 
+/* ---- co-visitation baseline: "recommend what other readers of the same articles went on to read", item-to-item collaborative
+ * filtering over click sequences (the reference has no such baseline; the plain-Python brute force of tests/covisit_cases.py is the
+ * yardstick) -------------------------------------------------------------------------------------------------------------------
+ * SEQUENCES: sequence s of n_seqs (one user's clicks, oldest first) holds the entries [seq_offsets[s], seq_offsets[s + 1]) of
+ * seq_rows [n_entries] int32; seq_offsets [n_seqs + 1] int64 ascending from 0 to at most n_entries, empty sequences anywhere.  An
+ * entry at or past seq_offsets[n_seqs] belongs to no sequence.
+ *   ebn_cv_pair_keys_i64: with G = max_gap and K = symmetric ? 2 G : G, for entry i of sequence s and g = 1 .. G, j = i + g:
+ *     keys[i * K + g - 1]     = seq_rows[j] * n_rows + seq_rows[i]   matrix row = the article clicked LATER, column = the one before it
+ *     keys[i * K + G + g - 1] = seq_rows[i] * n_rows + seq_rows[j]   (symmetric only: the mirrored pair)
+ *   when j < seq_offsets[s + 1], both rows lie in [0, n_rows) and the rows differ; EBN_CV_NO_PAIR otherwise, and for every slot of an
+ *   entry without a sequence.  All n_entries * K slots are written and nothing else; seq_rows is read inside [0, n_entries) only.
+ *   One lane per entry, 256-entry workgroups: the sequence of an entry is found as ebn_window_counts_i32 finds an item's list (one
+ *   uniform search per workgroup, 256 staged boundaries in LDS, a fallback search behind a run of empty sequences); the slots of a
+ *   workgroup leave as consecutive 8-byte stores.
+ *   n_seqs / n_entries / n_rows outside [0, 2^31 - 1], max_gap < 1, with n_entries > 0 a NULL seq_rows / seq_offsets / keys or
+ *   n_seqs == 0: EBN_ERR_BAD_ARG; then max_gap > EBN_CV_MAX_GAP: EBN_ERR_UNSUPPORTED; then n_entries == 0: nothing to do (EBN_OK, no
+ *   launch).  symmetric: 0 or not 0.
+ * MATRIX: CSR over n_rows rows: row r holds the columns cols[indptr[r] .. indptr[r + 1]) int32, STRICTLY ASCENDING, with the values
+ * vals[...] fp32; indptr [n_rows + 1] int64, nnz entries.  S[c, h] is the stored value, 0 where nothing is stored.
+ * HISTORIES and LISTS: as for ebn_cs_nearest_scores_f32 above (hist_rows / hist_weights / hist_offsets, list_hist, cand_rows /
+ * cand_offsets); an entry or item whose row is outside [0, n_rows) is ABSENT; an entry that occurs twice counts twice.
+ *   ebn_cv_scores_f32: for item i of list l, c = cand_rows[i], u = list_hist ? list_hist[l] : l:
+ *     mode 0 (sum)  scores[i] = sum over the present entries j of history u of w_j * S[c, hist_rows[j]]
+ *     mode 1 (max)  scores[i] = max over the same entries of w_j * S[c, hist_rows[j]]
+ *   exactly 0.0f when the item is absent, u is outside [0, n_hists) or history u has no present entry.  All n_cand_items scores
+ *   are written and nothing else.  Whatever cols holds, cols and vals are read only at positions inside
+ *   [indptr[c], indptr[c + 1]) intersected with [0, nnz); the history extents are clamped to [0, n_hist_items] in the same way.
+ *   256-item workgroups: one lane per item finds its list, history extent and matrix row extent; then one wave per item, 4 items
+ *   per round: lane s takes the history entries s, s + 64, ... in order and binary-searches each present one in the row's columns;
+ *   a butterfly over the 64 lanes (xor 32 .. 1) adds or maximises the partials.  Each product and each add rounds once, the order
+ *   is fixed, no atomics, no workspace: two runs give the same bits.
+ *   n_rows / nnz / n_hists / n_hist_items / n_lists / n_cand_items outside [0, 2^31 - 1], mode outside {0, 1}, n_cand_items > 0 with
+ *   n_lists = 0, n_hist_items > 0 with n_hists = 0: EBN_ERR_BAD_ARG.  n_cand_items == 0: nothing to do (EBN_OK, no launch).  Otherwise
+ *   a NULL among the pointers the call needs is EBN_ERR_BAD_ARG; hist_weights and list_hist may be NULL, indptr with n_rows == 0,
+ *   cols and vals with nnz == 0, hist_offsets with n_hists == 0, hist_rows with n_hist_items == 0 (zeros in one launch).
+ * All checked on the host before the launch: a failing call writes nothing.                                                         */
+#define EBN_CV_MAX_GAP 64
+#define EBN_CV_NO_PAIR INT64_MAX /* a key slot without a pair; sorts behind every key */
+int ebn_cv_pair_keys_i64(const int32_t* seq_rows, const int64_t* seq_offsets, int64_t n_seqs, int64_t n_entries, int64_t n_rows,
+                         int32_t max_gap, int32_t symmetric, int64_t* keys, ebn_stream_t stream);
+int ebn_cv_scores_f32(const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int64_t nnz,
+                      const int32_t* hist_rows, const float* hist_weights, const int64_t* hist_offsets, int64_t n_hists,
+                      int64_t n_hist_items, const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets,
+                      int64_t n_lists, int64_t n_cand_items, int32_t mode, float* scores, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
