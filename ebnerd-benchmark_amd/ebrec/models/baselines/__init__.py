@@ -1,3 +1,4 @@
+from .als import ImplicitALS, als_loss_host, als_partials_host, als_scores_host, als_solve_host  # noqa: F401
 from .content import (  # noqa: F401
     ContentSimilarity, content_centroid_scores_host, content_nearest_scores_host, content_profiles_host, history_weight_values,
     unit_rows_host,

@@ -1451,6 +1451,48 @@ int ebn_cv_scores_f32(const int64_t* indptr, const int32_t* cols, const float* v
                       int64_t n_hist_items, const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets,
                       int64_t n_lists, int64_t n_cand_items, int32_t mode, float* scores, ebn_stream_t stream);
 
+/* ---- implicit-feedback ALS baseline (Hu, Koren, Volinsky 2008): latent-factor collaborative filtering, one half-sweep per call (the
+ * reference has no such baseline; the float64 brute force of tests/als_cases.py is the yardstick) ----------------------------------
+ * FIXED SIDE: fixed [n_fixed, F] fp32 at row stride ld >= F, used as it is; gram [F, F] at row stride ldg >= F is fixed^T fixed,
+ * computed by the caller (ebn_gemm_f32_ws with transA = 1); only its lower triangle i >= j is read.
+ * ROWS: CSR over n_solve rows: row r holds the entries [indptr[r], indptr[r + 1]) clamped to [0, nnz] of cols [nnz] int32 and
+ * conf [nnz] fp32 (a_k >= 0: the host's guarantee; used as it is); indptr [n_solve + 1] int64.  An entry whose column is outside
+ * [0, n_fixed) is ABSENT: it adds nothing and its column is never turned into an address.  Entries are used AS GIVEN: a repeated
+ * column counts twice -- the host layer combines duplicates (summing their confidences) before the call.
+ *   ebn_als_solve_f32: out[r * ldo + 0 .. F) = x_r, the solution of
+ *       (gram + reg I + sum_k a_k y_k y_k^T) x_r = sum_k (1 + a_k) y_k,     y_k = fixed[cols[k], :], a_k = conf[k],
+ *     over the present entries k of row r.  A row without a present entry gets exact +0.0 and no factorisation.  If a Cholesky
+ *     pivot is not > 0 (NaN included) the WHOLE output row is NaN (the host layer raises on it).  All n_solve * F outputs are
+ *     written and nothing else; columns >= F of fixed, gram and out are never read or written.
+ *     LONG ROWS: with row_parts [n_solve + 1] int64 non-NULL, n_parts > 0 and row_parts[r] < row_parts[r + 1] (both clamped to
+ *     [0, n_parts]) the kernel adds the parts [row_parts[r], row_parts[r + 1]) of `partials` in ascending order INSTEAD of walking
+ *     the row's entries (such a row is always factorised).  row_parts is ignored when n_parts == 0.
+ *   ebn_als_partials_f32: part p of n_parts covers the entries [part_begin[p], part_end[p]) clamped to [0, nnz] and writes
+ *     partials[p * F (F + 1) + ...]: first the FULL symmetric matrix sum_k a_k y_k y_k^T as F * F floats, row-major (element (i, j)
+ *     and (j, i) hold the same bits; the solve reads i >= j), then the F floats sum_k (1 + a_k) y_k.  All n_parts * F (F + 1)
+ *     floats are written and nothing else.  The host cuts only rows longer than its split_len into parts of at most split_len
+ *     entries: short rows never touch the workspace.
+ * One workgroup per row / part, a G x G grid of threads: 256 threads (G = 16) for F > 32, one wave (G = 8) for F <= 32.  A lives in
+ * registers (thread (ty, tx) owns the elements (ty + G a, tx + G b) of the blocks a >= b; F is rounded up to G, 2 G, 4 G or 8 G), the
+ * entries are staged 16 at a time as a [16, F] tile in LDS and taken in their order, a right-looking Cholesky runs on the
+ * registers with one column of L passing through LDS per step (two barriers a step), wave 0 does the two triangular solves.  Every product, add, fused multiply-add,
+ * correctly rounded sqrtf and division happens in one fixed order: no atomics, two runs and every placement give the same bits,
+ * and the bits do not depend on ld / ldg / ldo or on alignment (16-byte loads are used only where fixed and ld allow them).
+ * LDS: 4 (FB (FB + 1) + 18 FB + 72) bytes for FB = F rounded up: 73.8 KiB at 128 (two workgroups per CU), 21.0 KiB at 64.
+ * Any of n_fixed / F / ld / ldg / ldo / n_solve / nnz / n_parts outside [0, 2^31 - 1], F < 1, ld < F, ldg < F, ldo < F, reg not
+ * finite or not > 0, n_parts > 0 with NULL partials, a NULL among the pointers the call needs: EBN_ERR_BAD_ARG; then
+ * F > EBN_ALS_MAX_F: EBN_ERR_UNSUPPORTED.  Nothing to do (EBN_OK, no launch): n_solve == 0, or n_parts == 0 for the partials
+ * call.  cols / conf may be NULL with nnz == 0 and fixed with n_fixed == 0 or nnz == 0 (every entry is absent: zeros in one
+ * launch); row_parts may be NULL.  All checked on the host before the launch: a failing call launches and writes nothing.         */
+#define EBN_ALS_MAX_F 128
+int ebn_als_solve_f32(const float* fixed, int64_t n_fixed, int64_t F, int64_t ld, const float* gram, int64_t ldg,
+                      const int64_t* indptr, const int32_t* cols, const float* conf, int64_t n_solve, int64_t nnz, float reg,
+                      const int64_t* row_parts, const float* partials, int64_t n_parts, float* out, int64_t ldo,
+                      ebn_stream_t stream);
+int ebn_als_partials_f32(const float* fixed, int64_t n_fixed, int64_t F, int64_t ld, const int32_t* cols, const float* conf,
+                         int64_t nnz, const int64_t* part_begin, const int64_t* part_end, int64_t n_parts, float* partials,
+                         ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
