@@ -40,6 +40,7 @@ import numpy as np
 from ebrec.evaluation.device_metrics import RaggedLists, device_available
 from ebrec.utils._constants import DEFAULT_HISTORY_ARTICLE_ID_COL
 
+from ._topn import DenseSession, TopN
 from .content import ContentSimilarity, _keep_last, content_centroid_scores_host, history_weight_values
 from .popularity import _explode, _frame, _ragged_ids, _rows_of
 
@@ -309,7 +310,7 @@ def _solve_host(fixed, side, reg):
 
 
 # ---- the class -----------------------------------------------------------------------------------------------------------------
-class ImplicitALS:
+class ImplicitALS(TopN):
     """Implicit-feedback ALS.  ``factors``: F, 1 to 128; ``regularization``: reg > 0; ``alpha``: the confidence of one (unit-weight)
     occurrence; ``iterations``: sweeps (users, then items); ``seed``: of the initial item factors; ``history_weights`` /
     ``lambda_factor`` / ``history_size`` / ``fill``: as in ``ContentSimilarity``; ``split_len``: rows with more entries are cut into
@@ -469,6 +470,18 @@ class ImplicitALS:
         if self._gram is None:
             self._gram = gram_call(Y)
         return self._check(solve_call(Y, self._gram, side, self.regularization), "fold-in")
+
+    # -- recommend / rank_targets (TopN, _topn.py): the fold-in rows against the item factors through the existing dense top-k and
+    # target-rank launches; a history without a known article folds into a zero row and gets an empty list
+    def _topn_ids(self):
+        self._fitted()
+        return self.article_ids
+
+    def _topn_rows_of(self, ids):
+        return self.rows_of(ids)
+
+    def _topn_session(self, histories):
+        return DenseSession(self.fold_in(histories), self._fitted())
 
     def predict(self, candidates, histories=None, list_hist=None, *, history=None) -> RaggedLists:
         """float64 scores aligned with the candidate lists; the three call forms of ``ContentSimilarity.predict``:

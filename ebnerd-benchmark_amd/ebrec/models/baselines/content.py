@@ -27,6 +27,7 @@ from ebrec.evaluation.beyond_accuracy import DeviceLookup
 from ebrec.evaluation.device_metrics import RaggedLists, device_available
 from ebrec.utils._constants import DEFAULT_HISTORY_ARTICLE_ID_COL, DEFAULT_INVIEW_ARTICLES_COL, DEFAULT_USER_COL
 
+from ._topn import DenseSession, TopN
 from .popularity import _explode, _frame, _ragged_ids
 
 MAX_D = 1024  # EBN_CS_MAX_D of include/ebnerd_hip.h
@@ -176,7 +177,7 @@ def _keep_last(flat, offsets, size):
 
 
 # ---- the class -----------------------------------------------------------------------------------------------------------------
-class ContentSimilarity:
+class ContentSimilarity(TopN):
     """Centroid or nearest-history scores over a vector key of a ``DeviceLookup`` (or of a plain ``lookup_dict``, which is
     wrapped).  ``history_weights``: None (all 1), "linear", "exponential" (with ``lambda_factor``) or a callable
     ``n -> n weights, oldest first``; ``history_size``: keep each history's last n entries; ``fill``: the score of an unknown
@@ -264,6 +265,21 @@ class ContentSimilarity:
             _hip.call("ebn_cs_profiles_f32", _hip.ptr(table), table.shape[0], table.shape[1], table.stride(0), _hip.ptr(rows_d),
                       _hip.ptr(w_d), _hip.ptr(off_d), n_hists, rows_d.numel(), _hip.ptr(out), out.stride(0), _hip.stream_handle())
         return out
+
+    # -- recommend / rank_targets (TopN, _topn.py), centroid mode: the unit profiles against the unit table through the existing
+    # dense top-k and target-rank launches; a history without a known article has a zero profile and gets an empty list
+    def _topn_ids(self):
+        return self.lookup.ids
+
+    def _topn_rows_of(self, ids):
+        return self.lookup.rows_of(ids)
+
+    def _topn_session(self, histories):
+        if self.mode != "centroid":
+            raise NotImplementedError("recommend / rank_targets are not implemented for ContentSimilarity(mode='nearest'): only the "
+                                      "centroid profile is a dense user vector the top-k launches take")
+        table = self.lookup.device_table(self.key) if self._on_device() else self.host_unit_table()
+        return DenseSession(self.profiles(histories), table)
 
     def predict(self, candidates, histories=None, list_hist=None, *, history=None) -> RaggedLists:
         """float64 scores aligned with the candidate lists.  ``predict(behaviors, history=history_frame)``: joined on ``user_id``;

@@ -22,6 +22,13 @@ score of what cannot be scored, exactly where ``ContentSimilarity`` puts it: an 
 history article.  Histories, their weights, ``history_size`` and ``list_hist`` are those of content.py, whose helpers this module
 uses.
 
+TOP-N.  ``recommend`` / ``rank_targets`` (``TopN``, _topn.py) are the second outlet: each impression's best ``top_n`` of ALL fitted
+articles, and the full-catalogue rank of its clicked article, under history exclusion and freshness windows.  Only articles that
+were co-visited with at least one history article can be listed -- "never co-visited" is not "score 0" -- while a listed article may
+have a negative score.  On the device they run ``ebn_cv_topk_f32`` / ``ebn_cv_target_rank_f32`` (csrc/ebn_covisit_topk.hip) over the
+TRANSPOSED matrix (``CoVisitMatrix.transpose``, built at the first use); the numpy twins ``covisit_topk_host`` /
+``covisit_target_rank_host`` do the same float32 arithmetic in the same history order and are bit-equal to the kernels.
+
 Two paths, as in content.py.  With a visible GPU the pair keys come from ``ebn_cv_pair_keys_i64`` and the scores from
 ``ebn_cv_scores_f32`` (csrc/ebn_covisit.hip; contract in include/ebnerd_hip.h); between them torch sorts the keys, counts the
 runs of equal ones and finds the row starts.  The sequences are cut into blocks whose keys stay within ``max_keys`` (never inside
@@ -35,6 +42,7 @@ import numpy as np
 from ebrec.evaluation.device_metrics import RaggedLists, device_available
 from ebrec.utils._constants import DEFAULT_HISTORY_ARTICLE_ID_COL
 
+from ._topn import TopN
 from .content import ContentSimilarity, _keep_last, _list_histories, _present_entries, history_weight_values
 from .popularity import _explode, _frame, _ragged_ids, _rows_of
 
@@ -191,6 +199,140 @@ def covisit_scores_host(indptr, cols, vals, hist_rows, hist_weights, hist_offset
     return out
 
 
+# ---- top-N over the whole catalogue: the numpy twins of ebn_cv_topk_f32 / ebn_cv_target_rank_f32 ---------------------------------
+MAX_TOP_K, MAX_EXCLUDE, NO_POSITION = 64, 256, 2 ** 31 - 1  # limits of include/ebnerd_hip.h; the position of an empty list slot
+
+
+def covisit_transpose_host(indptr, cols, vals):
+    """the transpose of a square CSR matrix with ascending columns -> (t_indptr int64, t_cols int32 ascending per row, t_vals):
+    row h of the result holds every row c with a stored entry (c, h), and its value"""
+    indptr, cols, vals = np.asarray(indptr, np.int64).ravel(), np.asarray(cols).ravel(), np.asarray(vals).ravel()
+    n = indptr.size - 1
+    row_of = np.repeat(np.arange(n, dtype=np.int32), np.diff(indptr))
+    order = np.argsort(cols, kind="stable")  # stable: the rows of one column stay ascending
+    t_indptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(cols, minlength=n)[:n], out=t_indptr[1:])
+    return t_indptr, row_of[order], vals[order]
+
+
+def covisit_transpose_device(indptr, cols, vals):
+    """``covisit_transpose_host`` in torch on the matrix's device"""
+    import torch
+
+    n = indptr.numel() - 1
+    row_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=cols.device), indptr[1:] - indptr[:-1])
+    key, order = torch.sort(cols.long(), stable=True)
+    t_indptr = torch.zeros(n + 1, dtype=torch.int64, device=cols.device)
+    t_indptr[1:] = torch.cumsum(torch.bincount(key, minlength=n)[:n], 0)
+    return t_indptr, row_of[order].contiguous(), vals[order].contiguous()
+
+
+def _chain_host(t_indptr, t_cols, t_vals, rows, weights, mode):
+    """one user's scores over the whole catalogue in the kernel's arithmetic -> (touched [n_rows] bool, score [n_rows] float32):
+    the history entries in order, vectorised over the rows of each; every product and every add rounds once to float32"""
+    n_rows, nnz = t_indptr.size - 1, t_cols.size
+    touched, score = np.zeros(n_rows, bool), np.zeros(n_rows, np.float32)
+    with np.errstate(all="ignore"):
+        for j, h in enumerate(np.asarray(rows).tolist()):
+            if not 0 <= h < n_rows:
+                continue
+            a, b = (min(max(int(v), 0), nnz) for v in (t_indptr[h], t_indptr[h + 1]))
+            if a >= b:
+                continue
+            c = t_cols[a:b]
+            p = (np.float32(1.0) if weights is None else np.float32(weights[j])) * t_vals[a:b].astype(np.float32)
+            old = score[c]
+            later = np.where((p > old) | np.isnan(p), p, old) if mode == 1 else old + p
+            score[c] = np.where(touched[c], later, p).astype(np.float32)
+            touched[c] = True
+    return touched, score
+
+
+def covisit_chains_host(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, mode) -> list:
+    """[(touched [n_rows] bool, score [n_rows] float32)] per history: the part of the twins that depends on neither the candidates
+    nor the windows nor the exclusion lists (``chains=`` of both twins takes it, so that several calls share it)"""
+    mode = {"sum": 0, "max": 1}.get(mode, mode)
+    if mode not in (0, 1):
+        raise ValueError(f"mode must be 0 / 'sum' or 1 / 'max', got {mode!r}")
+    t_indptr, t_cols = np.asarray(t_indptr, np.int64).ravel(), np.asarray(t_cols, np.int64).ravel()
+    t_vals = np.asarray(t_vals, np.float32).ravel()
+    hist_rows, hist_offsets = np.asarray(hist_rows, np.int64).ravel(), np.asarray(hist_offsets, np.int64).ravel()
+    out = []
+    for h in range(hist_offsets.size - 1):
+        a, b = (min(max(int(v), 0), hist_rows.size) for v in (hist_offsets[h], hist_offsets[h + 1]))
+        w = None if hist_weights is None else np.asarray(hist_weights, np.float32).ravel()[a:b]
+        out.append(_chain_host(t_indptr, t_cols, t_vals, hist_rows[a:b], w, mode))
+    return out
+
+
+def _walk_host(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window, exclude, mode,
+               chains=None):
+    """per user: (admissible rows, their positions, the float32 scores of all rows), and the two flags at the end"""
+    if chains is None:
+        chains = covisit_chains_host(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, mode)
+    n_rows, n_hists = np.asarray(t_indptr).size - 1, len(chains)
+    pos_of = np.arange(n_rows, dtype=np.int64) if cand_pos is None else np.asarray(cand_pos, np.int64).ravel()
+    if pos_of.size != n_rows or (cand_pos is None and M != n_rows):
+        raise ValueError(f"cand_pos must hold one position per catalogue row ({n_rows}); without it M == n_rows")
+    flags = np.zeros(2, np.int32)
+    for u in range(int(n_users)):
+        h = u if user_hist is None else int(user_hist[u])
+        touched, score = np.zeros(n_rows, bool), np.zeros(n_rows, np.float32)
+        if 0 <= h < n_hists:
+            touched, score = chains[h]
+        lo, hi = 0, int(M)
+        if window is not None:
+            lo, hi = max(int(window[u][0]), 0), min(int(window[u][1]), int(M))
+            if lo >= hi:
+                lo = hi = 0
+        if (touched & (pos_of >= M)).any():
+            flags[0] = 1
+        adm = touched & (pos_of >= lo) & (pos_of < hi)
+        if exclude is not None:
+            ex = np.asarray(exclude[u], np.int64).ravel()
+            adm[ex[(ex >= 0) & (ex < n_rows)]] = False
+        if (adm & np.isnan(score)).any():
+            flags[1] = 1
+        adm &= ~np.isnan(score)
+        rows = np.flatnonzero(adm)
+        yield u, rows, pos_of[rows], score, flags
+
+
+def covisit_topk_host(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window, exclude,
+                      k, mode, chains=None):
+    """numpy twin of ebn_cv_topk_f32, bit-equal to it -> (pos [U, k] int32, score [U, k] float32, flags [2] int32)"""
+    if not 1 <= int(k) <= MAX_TOP_K:
+        raise ValueError(f"k must lie in [1, {MAX_TOP_K}], got {k}")
+    out_pos, out_score = np.full((int(n_users), int(k)), -1, np.int32), np.full((int(n_users), int(k)), -np.inf, np.float32)
+    flags = np.zeros(2, np.int32)
+    for u, rows, pos, score, flags in _walk_host(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos,
+                                                 M, window, exclude, mode, chains):
+        s = score[rows]
+        best = np.lexsort((pos, -s))[:int(k)]  # score descending, then position ascending
+        out_pos[u, :best.size], out_score[u, :best.size] = pos[best], s[best]
+    return out_pos, out_score, flags
+
+
+def covisit_target_rank_host(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, target_pos,
+                             window, exclude, mode, chains=None):
+    """numpy twin of ebn_cv_target_rank_f32 -> (rank [U] int32, count [U] int32, score [U] float32, flags [2] int32)"""
+    target_pos = np.asarray(target_pos, np.int64).ravel()
+    U = int(n_users)
+    rank, count, t_out = np.zeros(U, np.int32), np.zeros(U, np.int32), np.full(U, -np.inf, np.float32)
+    flags, oob_target = np.zeros(2, np.int32), bool((target_pos[:U] >= M).any())
+    for u, rows, pos, score, flags in _walk_host(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos,
+                                                 M, window, exclude, mode, chains):
+        count[u] = rows.size
+        at = np.flatnonzero(pos == target_pos[u]) if 0 <= target_pos[u] < M else np.zeros(0, np.int64)
+        if at.size:
+            s, t = score[rows], score[rows[at[0]]]
+            rank[u] = 1 + int(((s > t) | ((s == t) & (pos < target_pos[u]))).sum())
+            t_out[u] = t
+    if oob_target:
+        flags[0] = 1
+    return rank, count, t_out, flags
+
+
 # ---- the matrix ----------------------------------------------------------------------------------------------------------------
 class CoVisitMatrix:
     """``article_ids`` (sorted, numpy) name the rows and columns; ``indptr`` int64 [n_rows + 1], ``cols`` int32, ``counts`` int32 and
@@ -198,7 +340,22 @@ class CoVisitMatrix:
 
     def __init__(self, article_ids, indptr, cols, counts, vals):
         self.article_ids, self.indptr, self.cols, self.counts, self.vals = article_ids, indptr, cols, counts, vals
-        self._host = None
+        self._host = self._transpose = self._transpose_host = None
+
+    def transpose(self):
+        """(t_indptr, t_cols, t_vals): the transposed CSR the catalogue kernels walk, where the matrix lives (device tensors on the
+        device path); built at the first use and kept"""
+        if self._transpose is None:
+            build = covisit_transpose_device if self.on_device else covisit_transpose_host
+            self._transpose = build(self.indptr, self.cols, self.vals)
+        return self._transpose
+
+    def transpose_host(self):
+        """the same as numpy arrays, downloaded (or built) once"""
+        if self._transpose_host is None:
+            t = self.transpose()
+            self._transpose_host = tuple(p.cpu().numpy() for p in t) if self.on_device else t
+        return self._transpose_host
 
     @property
     def on_device(self) -> bool:
@@ -310,8 +467,136 @@ def scores_call(indptr, cols, vals, hist_rows, hist_weights, hist_offsets, list_
     return scores
 
 
+def _cv_operands(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, cand_pos, M):
+    from ebrec import _hip
+
+    n_rows = t_indptr.numel() - 1
+    M = n_rows if cand_pos is None else int(M)
+    return (_hip.ptr(t_indptr), _hip.ptr(t_cols), _hip.ptr(t_vals), n_rows, t_cols.numel(), _hip.ptr(hist_rows), _hip.ptr(hist_weights),
+            _hip.ptr(hist_offsets), hist_offsets.numel() - 1, hist_rows.numel(), _hip.ptr(user_hist), _hip.ptr(cand_pos), M), n_rows
+
+
+def _check_device_args(U, window, exclude, target_pos=None):
+    import torch
+
+    for name, t, shape in (("window", window, (U, 2)), ("exclude", exclude, None), ("target_pos", target_pos, (U,))):
+        if t is None:
+            continue
+        if t.dtype != torch.int32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape) or \
+                (shape is None and (t.dim() != 2 or t.shape[0] != U)):
+            raise ValueError(f"{name} must be a contiguous int32 tensor with one row per user ({U}), got {tuple(t.shape)} {t.dtype}")
+
+
+def topk_call(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window, exclude, k, mode,
+              flags, n_splits: int = 0):
+    """One ebn_cv_topk_f32 launch over device tensors (``hist_weights`` / ``user_hist`` / ``cand_pos`` / ``window`` [U, 2] /
+    ``exclude`` [U, X] may be None) -> (pos [U, k] int32, score [U, k] float32); ``flags`` [2] int32 accumulates."""
+    import torch
+
+    from ebrec import _hip
+
+    U, dev = int(n_users), t_indptr.device
+    _check_device_args(U, window, exclude)
+    ops, n_rows = _cv_operands(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, cand_pos, M)
+    pos = torch.empty(U, k, dtype=torch.int32, device=dev)
+    score = torch.empty(U, k, dtype=torch.float32, device=dev)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_cv_topk_auto_splits(U, n_rows))
+    ws = torch.empty(max(int(lib.ebn_cv_topk_workspace_bytes(U, k, max(splits, 1))), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("ebn_cv_topk_f32", *ops, _hip.ptr(window), _hip.ptr(exclude), 0 if exclude is None else exclude.shape[1], int(k), int(mode),
+                  splits, _hip.ptr(pos), _hip.ptr(score), _hip.ptr(flags), _hip.ptr(ws), ws.numel(), U, _hip.stream_handle())
+    return pos, score
+
+
+def target_rank_call(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, target_pos, window,
+                     exclude, mode, flags, n_splits: int = 0):
+    """One ebn_cv_target_rank_f32 launch over device tensors: ``target_pos`` [U] int32 candidate positions (< 0: none) -> (rank [U]
+    int32: 1-based place in ``topk_call``'s order, 0 = not ranked; count [U] int32: the user's admissible rows; score [U] float32:
+    the target's score, -inf where rank is 0); ``flags`` accumulates."""
+    import torch
+
+    from ebrec import _hip
+
+    U, dev = int(n_users), t_indptr.device
+    _check_device_args(U, window, exclude, target_pos)
+    ops, n_rows = _cv_operands(t_indptr, t_cols, t_vals, hist_rows, hist_weights, hist_offsets, user_hist, cand_pos, M)
+    rank = torch.empty(U, dtype=torch.int32, device=dev)
+    count = torch.empty(U, dtype=torch.int32, device=dev)
+    score = torch.empty(U, dtype=torch.float32, device=dev)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_cv_topk_auto_splits(U, n_rows))
+    ws = torch.empty(max(int(lib.ebn_cv_target_rank_workspace_bytes(U, max(splits, 1), 0 if cand_pos is None else int(M))), 16),
+                     dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("ebn_cv_target_rank_f32", *ops, _hip.ptr(target_pos), _hip.ptr(window), _hip.ptr(exclude),
+                  0 if exclude is None else exclude.shape[1], int(mode), splits, _hip.ptr(rank), _hip.ptr(count), _hip.ptr(score),
+                  _hip.ptr(flags), _hip.ptr(ws), ws.numel(), U, _hip.stream_handle())
+    return rank, count, score
+
+
+class _CoVisitSession:
+    """what ``TopN`` drives (see _topn.py): the histories of one ``recommend`` / ``rank_targets`` call against the transposed matrix;
+    device tensors and the two kernels when the matrix lives on the device, the float32 twins otherwise"""
+
+    def __init__(self, matrix: CoVisitMatrix, h_rows, h_off, w, mode: int, on_device: bool):
+        self.on_device, self.mode, self.n_rows = on_device, mode, matrix.n_rows
+        self.cand_pos, self.M = None, matrix.n_rows
+        if on_device:
+            import torch
+
+            self.device = matrix.indptr.device
+            up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            self.t = matrix.transpose()
+            self.hist = (up(h_rows.astype(np.int32)), up(w), up(np.ascontiguousarray(h_off, dtype=np.int64)))
+        else:
+            self.t = matrix.transpose_host()
+            self.hist = (h_rows, w, np.ascontiguousarray(h_off, dtype=np.int64))
+            self.chains = covisit_chains_host(*self.t, *self.hist, mode)  # once for every batch of the call
+
+    def candidates(self, cand_rows):
+        """position -> row becomes the kernels' row -> position (-1: no candidate); the identity is passed as None"""
+        rows = np.asarray(cand_rows, np.int64)
+        self.M = rows.size
+        if rows.size == self.n_rows and np.array_equal(rows, np.arange(self.n_rows)):
+            self.cand_pos = None
+            return
+        pos = np.full(self.n_rows, -1, np.int32)
+        pos[rows] = np.arange(rows.size, dtype=np.int32)
+        self.cand_pos = pos
+        if self.on_device:
+            import torch
+
+            self.cand_pos = torch.from_numpy(pos).to(self.device)
+
+    def _up(self, a):
+        import torch
+
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    def topk(self, hist_idx, window, exclude, k, flags):
+        U = len(hist_idx)
+        if not self.on_device:
+            pos, score, f = covisit_topk_host(*self.t, *self.hist, hist_idx, U, self.cand_pos, self.M, window, exclude, k, self.mode,
+                                              self.chains)
+            flags |= f
+            return pos, score
+        return topk_call(*self.t, *self.hist, self._up(hist_idx), U, self.cand_pos, self.M, self._up(window), self._up(exclude), k,
+                         self.mode, flags)
+
+    def rank(self, hist_idx, target_pos, window, exclude, flags):
+        U = len(hist_idx)
+        if not self.on_device:
+            rank, count, score, f = covisit_target_rank_host(*self.t, *self.hist, hist_idx, U, self.cand_pos, self.M, target_pos, window,
+                                                             exclude, self.mode, self.chains)
+            flags |= f
+            return rank, count, score
+        return target_rank_call(*self.t, *self.hist, self._up(hist_idx), U, self.cand_pos, self.M, self._up(target_pos), self._up(window),
+                                self._up(exclude), self.mode, flags)
+
+
 # ---- the class -----------------------------------------------------------------------------------------------------------------
-class CoVisitation:
+class CoVisitation(TopN):
     """Item-to-item co-visitation scores.  ``max_gap``: how many later clicks of a sequence an article is paired with (1 to 64);
     ``symmetric``: count every pair in both directions; ``similarity``: "count", "cosine" or "conditional"; ``mode``: "sum" or
     "max" over the history; ``history_weights`` / ``lambda_factor`` / ``history_size`` / ``fill``: as in ``ContentSimilarity``;
@@ -376,6 +661,19 @@ class CoVisitation:
             flat, offsets = _keep_last(flat, offsets, self.history_size)
         w = history_weight_values(self.history_weights, offsets, self.lambda_factor)
         return self.rows_of(flat), np.ascontiguousarray(offsets, dtype=np.int64), (None if w is None else w.astype(np.float32))
+
+    # -- recommend / rank_targets (TopN, _topn.py): ebn_cv_topk_f32 / ebn_cv_target_rank_f32 over the transposed matrix.  A row no
+    # history article was ever co-visited with is never listed; a row with a negative score is
+    def _topn_ids(self):
+        return self._fitted().article_ids
+
+    def _topn_rows_of(self, ids):
+        return self.rows_of(ids)
+
+    def _topn_session(self, histories):
+        m = self._fitted()
+        h_rows, h_off, w = self._histories(histories)
+        return _CoVisitSession(m, h_rows, h_off, w, MODES.index(self.mode), m.on_device and device_available(self.device))
 
     # -- public
     def predict(self, candidates, histories=None, list_hist=None, *, history=None) -> RaggedLists:

@@ -15,6 +15,11 @@ baseline and writes one zipped submission file per baseline into --dump_dir:
   * als (with --als): implicit-feedback ALS (``ImplicitALS``: 64 factors, regularization 0.01, alpha 40, 15 sweeps), fitted on
     train/history.parquet; each user's validation/history.parquet is folded into the factor space and scored by dot products.
 
+--topn K adds, for each of covisit and als that is selected, the full-catalogue view (``recommend`` / ``rank_targets``): where the
+clicked article stands among ALL fitted articles under the user's validation history (hit-rate@K, MRR, nDCG@K,
+``ebrec.evaluation.rank_metrics``) and what the K-lists look like beyond accuracy: coverage of the fitted catalogue and novelty
+(mean -log2 of an article's share of the train-history clicks, relative to the most clicked one).
+
 With --device_metrics the counts, the ranking and the metrics run on the GPU; without it everything runs on the host."""
 from __future__ import annotations
 
@@ -29,7 +34,8 @@ import pandas as pd
 ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT / "ebnerd-benchmark_amd"))
 
-from ebrec.evaluation import AucScore, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore, RaggedLists  # noqa: E402
+from ebrec.evaluation import (AucScore, Coverage, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore, Novelty,  # noqa: E402
+                              RaggedLists, rank_metrics)
 from ebrec.models import (ArticleFeatureBaseline, CoVisitation, ImplicitALS, InviewEstimateBaseline, PopularityIndex,  # noqa: E402
                           RecentPopularity)
 from ebrec.utils._constants import (DEFAULT_CLICKED_ARTICLES_COL, DEFAULT_HISTORY_ARTICLE_ID_COL,  # noqa: E402
@@ -52,7 +58,23 @@ def get_args(argv=None):
     ap.add_argument("--index_validation_clicks", action="store_true", help="count the evaluated impressions' earlier clicks too")
     ap.add_argument("--covisit", action="store_true", help="add the co-visitation baseline (fit on the train history)")
     ap.add_argument("--als", action="store_true", help="add the implicit-ALS baseline (fit on the train history)")
+    ap.add_argument("--topn", type=int, default=0, metavar="K", help="also rank the clicked articles among ALL fitted articles and judge the "
+                    "top-K lists (covisit / als), 1 to 64")
     return ap.parse_args(argv)
+
+
+def topn_report(name, model, catalogue, df, df_val_history, df_history, k):
+    """hit-rate@k / MRR / nDCG@k of the clicked articles over the whole fitted catalogue, coverage and novelty of the k-lists"""
+    ranks = model.rank_targets(df, history=df_val_history)
+    out = {m: v for m, v in rank_metrics(ranks.rank, ks=(k,), counts=ranks.count).items()}
+    lists = model.recommend(df, history=df_val_history, top_n=k)
+    out["coverage"] = Coverage()([row[row >= 0] for row in lists], catalogue)[1]
+    ids, clicks = np.unique(np.concatenate([np.asarray(x).ravel() for x in df_history[DEFAULT_HISTORY_ARTICLE_ID_COL]]), return_counts=True)
+    popularity = {int(a): {"popularity": float(c) / float(clicks.max())} for a, c in zip(ids, clicks)}
+    novelty = Novelty()([row[row >= 0] for row in lists if (row >= 0).any()], popularity, "popularity")
+    out["novelty"] = float(np.mean(novelty)) if len(novelty) else float("nan")
+    print(f"{name} top-{k} over {len(catalogue)} articles: " + "  ".join(f"{m} {v:.4f}" for m, v in out.items()))
+    return out
 
 
 def labels_of(df) -> RaggedLists:
@@ -75,7 +97,9 @@ def main(argv=None):
     df_history = pd.read_parquet(PATH / args.datasplit / "train" / "history.parquet")
     df = pd.read_parquet(PATH / args.datasplit / "validation" / "behaviors.parquet")
 
-    baselines, skipped = {}, {}
+    baselines, skipped, topn = {}, {}, {}
+    if args.topn and not 1 <= args.topn <= 64:
+        raise SystemExit("--topn takes 1 to 64")
     for name, column in FEATURES.items():
         if column in df_articles.columns:
             baselines[name] = ArticleFeatureBaseline(df_articles, column).predict
@@ -101,6 +125,7 @@ def main(argv=None):
             df_val_history = pd.read_parquet(PATH / args.datasplit / "validation" / "history.parquet")
             print(f"covisit: {cv.matrix.nnz} pairs of {cv.matrix.n_rows} articles, max gap 3, cosine, sum")
             baselines["covisit_prediction_scores"] = lambda frame: cv.predict(frame, history=df_val_history)
+            topn["covisit"] = (cv, cv.matrix.article_ids, df_val_history)
         else:
             skipped["covisit_prediction_scores"] = f"history.parquet has no column '{DEFAULT_HISTORY_ARTICLE_ID_COL}'"
     if args.als:
@@ -109,6 +134,7 @@ def main(argv=None):
             df_als_history = pd.read_parquet(PATH / args.datasplit / "validation" / "history.parquet")
             print(f"als: {als.factors} factors of {len(als.article_ids)} articles and {len(df_history)} users, regularization 0.01, alpha 40, 15 sweeps")
             baselines["als_prediction_scores"] = lambda frame: als.predict(frame, history=df_als_history)
+            topn["als"] = (als, als.article_ids, df_als_history)
         else:
             skipped["als_prediction_scores"] = f"history.parquet has no column '{DEFAULT_HISTORY_ARTICLE_ID_COL}'"
     for name, why in skipped.items():
@@ -131,6 +157,9 @@ def main(argv=None):
         write_submission_file(impression_ids=df[DEFAULT_IMPRESSION_ID_COL].tolist(),
                               prediction_scores=rank_predictions_by_score_ragged(scores, device=device),
                               path=dump / "predictions.txt", filename_zip=f"{name}.zip")
+    if args.topn:
+        for name, (model, catalogue, val_history) in topn.items():
+            results[f"{name}_top{args.topn}"] = topn_report(name, model, catalogue, df, val_history, df_history, args.topn)
     return results, skipped
 
 

@@ -1451,6 +1451,69 @@ int ebn_cv_scores_f32(const int64_t* indptr, const int32_t* cols, const float* v
                       int64_t n_hist_items, const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets,
                       int64_t n_lists, int64_t n_cand_items, int32_t mode, float* scores, ebn_stream_t stream);
 
+/* ---- co-visitation top-N lists and clicked-article ranks over the whole catalogue (csrc/ebn_covisit_topk.hip; the plain-Python
+ * brute force of tests/covisit_topn_cases.py is the yardstick): what ebn_topk_score_window_f32 and ebn_target_rank_f32 are to the
+ * dense scorers, for the sparse score of ebn_cv_scores_f32 ------------------------------------------------------------------------
+ * Everything not said here is ebn_cv_scores_f32's (the CSR operand rules, the clamping of offsets to [0, nnz] and [0, n_hist_items],
+ * ABSENT entries, repeated entries counting twice) and ebn_topk_score_window_f32's (window [U, 2] and its clamping to [0, M),
+ * exclude [U, X] matching by catalogue row with -1 matching nothing, the total order, flags [2] only ever SET, all argument checks
+ * on the host before anything is launched: a failing call writes nothing).
+ * MATRIX: T, the TRANSPOSE of the fitted matrix, as CSR: t_indptr [n_rows + 1] int64, t_cols [nnz] int32 STRICTLY ASCENDING per row,
+ * t_vals [nnz] fp32: row h of T holds every catalogue row c with a stored S[c, h], and the value.
+ * HISTORIES: hist_rows / hist_weights (NULL: every weight 1) / hist_offsets over n_hists histories and n_hist_items entries; user u
+ * of U uses history user_hist ? user_hist[u] : u, an index outside [0, n_hists) is a user without history.
+ * POSITIONS: cand_pos [n_rows] int32 or NULL: the candidate position of catalogue row r; negative: the row is no candidate; NULL:
+ * position = row (then M == n_rows, else EBN_ERR_BAD_ARG).  A value >= M is skipped and sets flags[0] when some user touches the
+ * row.  Positions of distinct rows are distinct: the host's guarantee.
+ * SCORE: row c is TOUCHED by user u when at least one present entry j of u's history has a stored S[c, hist_rows[j]] (a stored 0.0
+ * counts).  With p_j = w_j * S[c, hist_rows[j]]: the score starts as the first touching entry's p_j; every later touching entry, in
+ * history order, does acc = acc + p_j (mode 0) or acc = (p_j > acc or p_j is NaN) ? p_j : acc (mode 1).  Every product and every
+ * add rounds once to fp32 (no fused multiply-add).  A score's bits depend on that user's history and that row's stored values
+ * only: not on U, M, n_splits, the run or the other users of the launch.  No floating-point atomics.
+ * ADMISSIBLE: row c for user u when it is touched, cand_pos[c] lies in [0, M) and in u's clamped window, c is not in exclude[u, :]
+ * and the score is not NaN.  A NaN score of a touched row that is admissible otherwise sets flags[1]; +-inf rank like numbers.  An
+ * untouched row never enters a list; a touched row with a negative score does.
+ *   ebn_cv_topk_f32: out_pos [U, k] / out_score [U, k]: each user's best k admissible rows as (position, score), score descending,
+ *     then position ascending; -1 / -inf in the empty trailing slots.  1 <= k <= 64.
+ *   ebn_cv_target_rank_f32: target_pos [U] int32 on the DEVICE (required).  out_rank / out_count / out_score as ebn_target_rank_f32
+ *     defines them, over this admissible set; the rank is 0 (score -inf) when there is no target (< 0; >= M also sets flags[0]),
+ *     the position belongs to no row, or the target's row is untouched or not admissible (a NaN t of a row admissible otherwise
+ *     sets flags[1]).  t has the bits ebn_cv_topk_f32 gives the same (user, row) pair.
+ * One 256-thread workgroup per (user, split) walks ranges of ebn_cv_topk_range() catalogue rows, an fp32 tile and two bits per row
+ * in LDS (34 KiB): per present history entry the segment of T's row inside the range (two binary searches), the threads stride
+ * over it, one barrier between entries.  n_splits: 0 = ebn_cv_topk_auto_splits(U, n_rows); clamped to the number of ranges and to
+ * 64.  More than one split: partial lists in the layout of ebn_topk_workspace_bytes (ebn_cv_topk_workspace_bytes gives the same
+ * number) merged by a second launch; partial counts ([2, n_splits, U] int32, then [U] fp32) added by a second launch.  The
+ * workspace is 16-byte aligned (else EBN_ERR_ALIGN) and at least that large (else, or NULL: EBN_ERR_BAD_ARG).  Results are
+ * bit-identical for every n_splits and from run to run.
+ * Any of n_rows / nnz / n_hists / n_hist_items / M / U outside [0, 2^31 - 1], X < 0, n_splits < 0, workspace_bytes < 0, mode
+ * outside {0, 1}, n_hist_items > 0 with n_hists = 0, cand_pos NULL with M != n_rows: EBN_ERR_BAD_ARG; then k outside [1, 64] or
+ * X > 256: EBN_ERR_UNSUPPORTED; then U == 0: nothing to do (EBN_OK, no launch); then a NULL output, flags or target_pos:
+ * EBN_ERR_BAD_ARG; then n_rows == 0, nnz == 0 or M == 0: empty outputs in one launch (-1 / -inf; rank 0, count 0, -inf, and
+ * flags[0] for a target position >= M); then a NULL t_indptr / t_cols / t_vals, hist_offsets with n_hists > 0 or hist_rows with
+ * n_hist_items > 0: EBN_ERR_BAD_ARG.  hist_weights, user_hist, cand_pos, window and exclude (then X counts as 0) may be NULL.      */
+/* The catalogue rows one LDS tile covers.  Pure host query.                                                                        */
+int64_t ebn_cv_topk_range(void);
+/* The number of row ranges n_splits = 0 stands for: 1 once the users alone give about 16 384 workgroups.  Pure host query, >= 1.  */
+int ebn_cv_topk_auto_splits(int64_t n_users, int64_t n_rows);
+/* Bytes of workspace for n_splits >= 1 (a nominal 16 where none is needed: one split, and for the rank call no cand_pos); 0 for
+ * sizes outside the limits.  n_positions: M when the rank call gets a cand_pos, else 0 -- the call first writes the inverse of
+ * cand_pos, [M] int32, into the workspace (one launch over the rows, once per call), so that a target's row is one load and not
+ * a search.  Pure host queries.                                                                                                    */
+int64_t ebn_cv_topk_workspace_bytes(int64_t n_users, int32_t k, int32_t n_splits);
+int64_t ebn_cv_target_rank_workspace_bytes(int64_t n_users, int32_t n_splits, int64_t n_positions);
+int ebn_cv_topk_f32(const int64_t* t_indptr, const int32_t* t_cols, const float* t_vals, int64_t n_rows, int64_t nnz,
+                    const int32_t* hist_rows, const float* hist_weights, const int64_t* hist_offsets, int64_t n_hists,
+                    int64_t n_hist_items, const int32_t* user_hist, const int32_t* cand_pos, int64_t M, const int32_t* window,
+                    const int32_t* exclude, int32_t X, int32_t k, int32_t mode, int32_t n_splits, int32_t* out_pos, float* out_score,
+                    int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U, ebn_stream_t stream);
+int ebn_cv_target_rank_f32(const int64_t* t_indptr, const int32_t* t_cols, const float* t_vals, int64_t n_rows, int64_t nnz,
+                           const int32_t* hist_rows, const float* hist_weights, const int64_t* hist_offsets, int64_t n_hists,
+                           int64_t n_hist_items, const int32_t* user_hist, const int32_t* cand_pos, int64_t M, const int32_t* target_pos,
+                           const int32_t* window, const int32_t* exclude, int32_t X, int32_t mode, int32_t n_splits, int32_t* out_rank,
+                           int32_t* out_count, float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U,
+                           ebn_stream_t stream);
+
 /* ---- implicit-feedback ALS baseline (Hu, Koren, Volinsky 2008): latent-factor collaborative filtering, one half-sweep per call (the
  * reference has no such baseline; the float64 brute force of tests/als_cases.py is the yardstick) ----------------------------------
  * FIXED SIDE: fixed [n_fixed, F] fp32 at row stride ld >= F, used as it is; gram [F, F] at row stride ldg >= F is fixed^T fixed,
