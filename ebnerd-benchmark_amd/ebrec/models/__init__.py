@@ -4,3 +4,6 @@ from .baselines import (  # noqa: F401
     covisit_scores_host, covisit_target_rank_host, covisit_topk_host, covisit_transpose_host, covisit_values_host, dense_target_rank_host,
     dense_topk_host, lexicographic_scores, window_counts_host,
 )
+from .ensemble import (  # noqa: F401
+    RankFusion, ScoreBlend, blend_combine_host, blend_features_host, blend_sums_host,
+)

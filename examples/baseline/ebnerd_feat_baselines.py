@@ -20,6 +20,10 @@ clicked article stands among ALL fitted articles under the user's validation his
 ``ebrec.evaluation.rank_metrics``) and what the K-lists look like beyond accuracy: coverage of the fitted catalogue and novelty
 (mean -log2 of an article's share of the train-history clicks, relative to the most clicked one).
 
+--blend adds one more row, blend_prediction_scores: a ``ScoreBlend`` over every baseline the run computed (--blend_transform: the per-list
+transform of every column, zscore by default), cross-fitted in 5 folds by ``user_id`` so that no impression is judged with weights
+fitted on it or on another impression of its user; the mean fold weights per source are printed next to its metrics.
+
 With --device_metrics the counts, the ranking and the metrics run on the GPU; without it everything runs on the host."""
 from __future__ import annotations
 
@@ -37,11 +41,11 @@ sys.path.insert(0, str(ROOT / "ebnerd-benchmark_amd"))
 from ebrec.evaluation import (AucScore, Coverage, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore, Novelty,  # noqa: E402
                               RaggedLists, rank_metrics)
 from ebrec.models import (ArticleFeatureBaseline, CoVisitation, ImplicitALS, InviewEstimateBaseline, PopularityIndex,  # noqa: E402
-                          RecentPopularity)
+                          RecentPopularity, ScoreBlend)
 from ebrec.utils._constants import (DEFAULT_CLICKED_ARTICLES_COL, DEFAULT_HISTORY_ARTICLE_ID_COL,  # noqa: E402
                                     DEFAULT_HISTORY_IMPRESSION_TIMESTAMP_COL, DEFAULT_IMPRESSION_ID_COL, DEFAULT_IMPRESSION_TIMESTAMP_COL,
                                     DEFAULT_INVIEW_ARTICLES_COL, DEFAULT_TOTAL_INVIEWS_COL, DEFAULT_TOTAL_PAGEVIEWS_COL,
-                                    DEFAULT_TOTAL_READ_TIME_COL)
+                                    DEFAULT_TOTAL_READ_TIME_COL, DEFAULT_USER_COL)
 from ebrec.utils._python import rank_predictions_by_score_ragged, write_submission_file  # noqa: E402
 
 WINDOWS = [dt.timedelta(hours=1), dt.timedelta(hours=6), dt.timedelta(hours=24)]
@@ -60,6 +64,9 @@ def get_args(argv=None):
     ap.add_argument("--als", action="store_true", help="add the implicit-ALS baseline (fit on the train history)")
     ap.add_argument("--topn", type=int, default=0, metavar="K", help="also rank the clicked articles among ALL fitted articles and judge the "
                     "top-K lists (covisit / als), 1 to 64")
+    ap.add_argument("--blend", action="store_true", help="add a cross-fitted blend of every baseline of the run (5 folds by user)")
+    ap.add_argument("--blend_transform", default="zscore", choices=["raw", "zscore", "minmax", "rank", "rrf"],
+                    help="per-list transform of every column before the blend")
     return ap.parse_args(argv)
 
 
@@ -144,9 +151,23 @@ def main(argv=None):
     metrics = [AucScore(), MrrScore(), NdcgScore(k=5), NdcgScore(k=10)]
     dump = Path(args.dump_dir)
     dump.mkdir(parents=True, exist_ok=True)
-    results = {}
+    results, columns = {}, {}
+    BLEND = "blend_prediction_scores"
+
+    def blend_predict(frame):
+        blend = ScoreBlend(transforms=args.blend_transform, device=device)
+        groups = frame[DEFAULT_USER_COL] if DEFAULT_USER_COL in frame.columns else None
+        scores, fold_weights = blend.cross_fit_predict(labels, list(columns.values()), folds=5, groups=groups)
+        print(f"blend: {len(columns)} sources, transform {args.blend_transform}, 5 folds by " + ("user" if groups is not None else "list") +
+              "; mean fold weights: " + "  ".join(f"{n} {w:.4f}" for n, w in zip(columns, fold_weights.mean(axis=0))))
+        return scores
+
+    if args.blend:
+        baselines[BLEND] = blend_predict
     for name, predict in baselines.items():
         scores = predict(df)
+        if args.blend and name != BLEND:
+            columns[name] = scores
         if args.device_metrics:
             ev = DeviceMetricEvaluator(labels, scores, metrics, device=device).evaluate()
         else:

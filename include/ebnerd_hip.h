@@ -1556,6 +1556,59 @@ int ebn_als_partials_f32(const float* fixed, int64_t n_fixed, int64_t F, int64_t
                          int64_t nnz, const int64_t* part_begin, const int64_t* part_end, int64_t n_parts, float* partials,
                          ebn_stream_t stream);
 
+/* ---- score blending over ragged lists (the reference has no such step; the plain-Python brute force of tests/blend_cases.py is the
+ * yardstick; host layer: ebrec/models/ensemble.py) -------------------------------------------------------------------------------
+ * SOURCES: scores [M, n_items], source-major, 1 <= M <= EBN_BL_MAX_SOURCES, all fp32 (score_kind EBN_RM_F32) or all fp64
+ * (EBN_RM_F64); compared and transformed in that type, unrounded.  All sources share one CSR offsets [n_lists + 1] int64; the
+ * conventions are those of ebn_rank_metrics: n_items <= 2^31 - 257, any list length (0 and 1 included), a list whose offsets leave
+ * [0, n_items] or run backwards is empty.  kinds [M] int32, params [M] fp64 and weights [M] fp64 are DEVICE arrays.
+ * TRANSFORMS: the feature of item i in a list of n, all arithmetic after the load in fp64, rounded once to fp32:
+ *   EBN_BL_RAW     s_i
+ *   EBN_BL_ZSCORE  (s_i - mean) / sd, two-pass population sd; 0 for every item when sd == 0 or max == min
+ *   EBN_BL_MINMAX  (s_i - min) / (max - min); 0 when max == min
+ *   EBN_BL_RANK    (n - r_i) / (n - 1) with the mid-rank r_i = 1 + #{s_j > s_i} + 0.5 #{j != i: s_j == s_i}; 0 when n == 1
+ *   EBN_BL_RRF     1 / (param + r_i)
+ *   any other kind: NaN.  mean and the sum of squares are summed over the list's items in ascending order.
+ * A list in which source m holds a non-finite score gets bit 1 (value 2) of flags[l] and NaN features in row m (RAW copies the
+ * scores through); flags[l] is written for every list, 0 otherwise.
+ *   ebn_blend_features_f32: features [M, n_items] fp32.  Every item of a well-formed list is written in every row, nothing else.
+ *   ebn_blend_combine_f64: out[i] = sum_m weights[m] * (double) feature_m,i, m ascending, of the SAME fp32-rounded features, with
+ *     no [M, n_items] intermediate; NaN for every item of a flagged list.
+ *   ebn_blend_sums_f64: over features [M, n_items] fp32 and labels [n_items] uint8 (non-zero = positive), at weights w, for list l
+ *       z = w . f (m ascending), p = softmax(z) with the maximum subtracted, t_i = y_i / n_pos, log p_i = (z_i - max) - log S,
+ *       loss_l = -(sum_i y_i log p_i) / n_pos,  g_l = sum_i (p_i - t_i) f_i,  u = sum_i p_i f_i,
+ *       H_l = sum_i p_i (f_i - u)(f_i - u)^T  (the centred form: positive semi-definite to rounding for features of any size);
+ *     sums [1 + M + M (M + 1) / 2] = the sum over the used lists of loss, g, and the upper triangle of H row-major (a <= b).
+ *     Skipped: one-class lists (no positive or no negative; empty lists included), then lists with a feature that is not finite.
+ *     counters [3] int64 = lists used, one-class, with such a feature.  n_lists == 0 writes zeros (one launch).
+ * FORMS: a 16-lane group per list of up to 16 items, half a wave up to 32, a wave up to 64, the workgroup beyond; form = 1 forces
+ * the workgroup form for every list (test hook), any other value but 0: EBN_ERR_BAD_ARG.  Every floating-point sum is taken in ONE
+ * order whatever the form (items ascending inside a list; lists ascending inside 16 slots per workgroup, slots ascending,
+ * workgroups through a closing launch), without atomics and without contraction: two runs, both forms and every placement give
+ * the same bits.
+ * M outside [1, 16], n_items outside [0, 2^31 - 257], n_lists outside [0, 2^31 - 1], an unknown score_kind, a NULL among the
+ * pointers (scores / features / labels / out may be NULL with n_items == 0; offsets and the workspace of the sums call with
+ * n_lists == 0), a workspace that is not 16-byte aligned or smaller than the query: EBN_ERR_BAD_ARG.  All checked on the host
+ * before the launch: a failing call launches and writes nothing.  n_lists == 0: nothing to do for features / combine.            */
+#define EBN_BL_MAX_SOURCES 16
+#define EBN_BL_RAW 0
+#define EBN_BL_ZSCORE 1
+#define EBN_BL_MINMAX 2
+#define EBN_BL_RANK 3
+#define EBN_BL_RRF 4
+int ebn_blend_features_f32(const void* scores, int32_t score_kind, int32_t M, int64_t n_items, const int64_t* offsets, int64_t n_lists,
+                           const int32_t* kinds, const double* params, int32_t form, float* features, uint8_t* flags,
+                           ebn_stream_t stream);
+int ebn_blend_combine_f64(const void* scores, int32_t score_kind, int32_t M, int64_t n_items, const int64_t* offsets, int64_t n_lists,
+                          const int32_t* kinds, const double* params, const double* weights, int32_t form, double* out, uint8_t* flags,
+                          ebn_stream_t stream);
+/* Bytes of the workspace ebn_blend_sums_f64 needs (one partial per entry and workgroup); 0 for n_lists or M outside their ranges.
+ * Pure host query.                                                                                                              */
+int64_t ebn_blend_sums_workspace_bytes(int64_t n_lists, int32_t M);
+int ebn_blend_sums_f64(const float* features, const uint8_t* labels, int32_t M, int64_t n_items, const int64_t* offsets, int64_t n_lists,
+                       const double* weights, int32_t form, double* sums, int64_t* counters, void* workspace, int64_t workspace_bytes,
+                       ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
