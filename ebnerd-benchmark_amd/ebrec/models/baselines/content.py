@@ -176,6 +176,41 @@ def _keep_last(flat, offsets, size):
     return flat[keep], out
 
 
+def history_operands(rows_of, histories, history_size, history_weights, lambda_factor):
+    """ids of histories -> (rows int32 by ``rows_of``, offsets int64, weights float32 | None): each history cut to its last
+    ``history_size`` entries, weighted by ``history_weight_values``"""
+    flat, offsets = _ragged_ids(histories)
+    if history_size is not None:
+        flat, offsets = _keep_last(flat, offsets, history_size)
+    w = history_weight_values(history_weights, offsets, lambda_factor)
+    return rows_of(flat), np.ascontiguousarray(offsets, dtype=np.int64), (None if w is None else w.astype(np.float32))
+
+
+def join_frames(behaviors, history):
+    """frames -> (candidates (flat ids, offsets), histories (flat ids, offsets), list_hist | None, users | None): with ``history`` one
+    history per distinct user, ``users[h]`` the user of history h and ``list_hist`` the join on ``user_id``; without it the
+    behaviours frame's own ``article_id_fixed`` per impression (list_hist and users None)"""
+    df = _frame(behaviors)
+    if DEFAULT_INVIEW_ARTICLES_COL not in df.columns:
+        raise ValueError(f"the behaviours frame lacks the column '{DEFAULT_INVIEW_ARTICLES_COL}'")
+    cand = _explode(df[DEFAULT_INVIEW_ARTICLES_COL])
+    if history is None:
+        if DEFAULT_HISTORY_ARTICLE_ID_COL not in df.columns:
+            raise ValueError(f"the behaviours frame lacks the column '{DEFAULT_HISTORY_ARTICLE_ID_COL}': pass history=")
+        return cand, _explode(df[DEFAULT_HISTORY_ARTICLE_ID_COL]), None, None
+    hf = _frame(history)
+    for frame, col in ((df, DEFAULT_USER_COL), (hf, DEFAULT_USER_COL), (hf, DEFAULT_HISTORY_ARTICLE_ID_COL)):
+        if col not in frame.columns:
+            raise ValueError(f"a frame lacks the column '{col}'")
+    users, first = np.unique(hf[DEFAULT_USER_COL].to_numpy(), return_index=True)  # one history per distinct user
+    hist = _explode(hf[DEFAULT_HISTORY_ARTICLE_ID_COL].iloc[first])
+    asked = df[DEFAULT_USER_COL].to_numpy()
+    if users.size == 0:
+        return cand, hist, np.full(asked.size, -1, np.int32), users
+    pos = np.minimum(np.searchsorted(users, asked), users.size - 1)
+    return cand, hist, np.where(users[pos] == asked, pos, -1).astype(np.int32), users
+
+
 # ---- the class -----------------------------------------------------------------------------------------------------------------
 class ContentSimilarity(TopN):
     """Centroid or nearest-history scores over a vector key of a ``DeviceLookup`` (or of a plain ``lookup_dict``, which is
@@ -213,33 +248,11 @@ class ContentSimilarity(TopN):
 
     def _histories(self, histories):
         """ids of histories -> (rows int32, offsets int64, weights float32 | None)"""
-        flat, offsets = _ragged_ids(histories)
-        if self.history_size is not None:
-            flat, offsets = _keep_last(flat, offsets, self.history_size)
-        w = history_weight_values(self.history_weights, offsets, self.lambda_factor)
-        return self.lookup.rows_of(flat), offsets, (None if w is None else w.astype(np.float32))
+        return history_operands(self.lookup.rows_of, histories, self.history_size, self.history_weights, self.lambda_factor)
 
     def _frames(self, behaviors, history):
         """frames -> (candidates (flat ids, offsets), histories (flat ids, offsets), list_hist | None)"""
-        df = _frame(behaviors)
-        if DEFAULT_INVIEW_ARTICLES_COL not in df.columns:
-            raise ValueError(f"the behaviours frame lacks the column '{DEFAULT_INVIEW_ARTICLES_COL}'")
-        cand = _explode(df[DEFAULT_INVIEW_ARTICLES_COL])
-        if history is None:
-            if DEFAULT_HISTORY_ARTICLE_ID_COL not in df.columns:
-                raise ValueError(f"the behaviours frame lacks the column '{DEFAULT_HISTORY_ARTICLE_ID_COL}': pass history=")
-            return cand, _explode(df[DEFAULT_HISTORY_ARTICLE_ID_COL]), None
-        hf = _frame(history)
-        for frame, col in ((df, DEFAULT_USER_COL), (hf, DEFAULT_USER_COL), (hf, DEFAULT_HISTORY_ARTICLE_ID_COL)):
-            if col not in frame.columns:
-                raise ValueError(f"a frame lacks the column '{col}'")
-        users, first = np.unique(hf[DEFAULT_USER_COL].to_numpy(), return_index=True)  # one history per distinct user
-        hist = _explode(hf[DEFAULT_HISTORY_ARTICLE_ID_COL].iloc[first])
-        asked = df[DEFAULT_USER_COL].to_numpy()
-        if users.size == 0:
-            return cand, hist, np.full(asked.size, -1, np.int32)
-        pos = np.minimum(np.searchsorted(users, asked), users.size - 1)
-        return cand, hist, np.where(users[pos] == asked, pos, -1).astype(np.int32)
+        return join_frames(behaviors, history)[:3]
 
     # -- public
     def profiles(self, histories):

@@ -13,7 +13,10 @@ baseline and writes one zipped submission file per baseline into --dump_dir:
   * covisit (with --covisit): item-to-item co-visitation (``CoVisitation``: max gap 3, both directions, cosine, summed over the
     user's history), counted over train/history.parquet and scored against each user's validation/history.parquet;
   * als (with --als): implicit-feedback ALS (``ImplicitALS``: 64 factors, regularization 0.01, alpha 40, 15 sweeps), fitted on
-    train/history.parquet; each user's validation/history.parquet is folded into the factor space and scored by dot products.
+    train/history.parquet; each user's validation/history.parquet is folded into the factor space and scored by dot products;
+  * knn (with --knn): sequence-neighbourhood collaborative filtering (``HistoryKNN``: the 100 nearest of the 1000 most recent train
+    histories that share an article with the user's validation history, cosine, linear history weights, the user's own train
+    history excluded), fitted on train/history.parquet.
 
 --topn K adds, for each of covisit and als that is selected, the full-catalogue view (``recommend`` / ``rank_targets``): where the
 clicked article stands among ALL fitted articles under the user's validation history (hit-rate@K, MRR, nDCG@K,
@@ -40,8 +43,8 @@ sys.path.insert(0, str(ROOT / "ebnerd-benchmark_amd"))
 
 from ebrec.evaluation import (AucScore, Coverage, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore, Novelty,  # noqa: E402
                               RaggedLists, rank_metrics)
-from ebrec.models import (ArticleFeatureBaseline, CoVisitation, ImplicitALS, InviewEstimateBaseline, PopularityIndex,  # noqa: E402
-                          RecentPopularity, ScoreBlend)
+from ebrec.models import (ArticleFeatureBaseline, CoVisitation, HistoryKNN, ImplicitALS, InviewEstimateBaseline,  # noqa: E402
+                          PopularityIndex, RecentPopularity, ScoreBlend)
 from ebrec.utils._constants import (DEFAULT_CLICKED_ARTICLES_COL, DEFAULT_HISTORY_ARTICLE_ID_COL,  # noqa: E402
                                     DEFAULT_HISTORY_IMPRESSION_TIMESTAMP_COL, DEFAULT_IMPRESSION_ID_COL, DEFAULT_IMPRESSION_TIMESTAMP_COL,
                                     DEFAULT_INVIEW_ARTICLES_COL, DEFAULT_TOTAL_INVIEWS_COL, DEFAULT_TOTAL_PAGEVIEWS_COL,
@@ -62,6 +65,7 @@ def get_args(argv=None):
     ap.add_argument("--index_validation_clicks", action="store_true", help="count the evaluated impressions' earlier clicks too")
     ap.add_argument("--covisit", action="store_true", help="add the co-visitation baseline (fit on the train history)")
     ap.add_argument("--als", action="store_true", help="add the implicit-ALS baseline (fit on the train history)")
+    ap.add_argument("--knn", action="store_true", help="add the history-kNN baseline (fit on the train history)")
     ap.add_argument("--topn", type=int, default=0, metavar="K", help="also rank the clicked articles among ALL fitted articles and judge the "
                     "top-K lists (covisit / als), 1 to 64")
     ap.add_argument("--blend", action="store_true", help="add a cross-fitted blend of every baseline of the run (5 folds by user)")
@@ -144,6 +148,14 @@ def main(argv=None):
             topn["als"] = (als, als.article_ids, df_als_history)
         else:
             skipped["als_prediction_scores"] = f"history.parquet has no column '{DEFAULT_HISTORY_ARTICLE_ID_COL}'"
+    if args.knn:
+        if DEFAULT_HISTORY_ARTICLE_ID_COL in df_history.columns:
+            knn = HistoryKNN(k=100, sample_size=1000, similarity="cosine", history_weights="linear", device=device).fit(df_history)
+            df_knn_history = pd.read_parquet(PATH / args.datasplit / "validation" / "history.parquet")
+            print(f"knn: {knn.index.n_seqs} sequences of {knn.index.n_rows} articles, k 100 of the 1000 most recent, cosine, linear weights")
+            baselines["knn_prediction_scores"] = lambda frame: knn.predict(frame, history=df_knn_history)
+        else:
+            skipped["knn_prediction_scores"] = f"history.parquet has no column '{DEFAULT_HISTORY_ARTICLE_ID_COL}'"
     for name, why in skipped.items():
         print(f"skipped {name}: {why}")
 

@@ -1609,6 +1609,71 @@ int ebn_blend_sums_f64(const float* features, const uint8_t* labels, int32_t M, 
                        const double* weights, int32_t form, double* sums, int64_t* counters, void* workspace, int64_t workspace_bytes,
                        ebn_stream_t stream);
 
+/* ---- history-kNN baseline (S-KNN / V-SKNN, Jannach & Ludewig 2017): neighbourhood collaborative filtering over whole click
+ * sequences, "find the readers whose sequences look most like this one, and recommend what they read" (the reference has no such
+ * baseline; the plain-Python brute force of tests/knn_cases.py is the yardstick; host layer: ebrec/models/baselines/knn.py) ------
+ * FITTED DATA: n_seqs training sequences over n_rows catalogue rows; the host orders them by recency: sequence id s ASCENDS from
+ * the oldest to the most recent.  Two CSR structures:
+ *   POSTINGS  p_indptr [n_rows + 1] int64, p_seqs [nnz_p] int32 STRICTLY ASCENDING per row: the distinct sequences that hold the row
+ *   SETS      s_indptr [n_seqs + 1] int64, s_items [nnz_s] int32 STRICTLY ASCENDING per sequence: its distinct rows
+ * Every extent read from p_indptr / s_indptr / hist_offsets is clamped to its array ([0, nnz_p], [0, nnz_s], [0, n_hist_items])
+ * before use, an extent that runs backwards is empty, and an id read from p_seqs addresses nothing before it is checked against
+ * its range: whatever the arrays hold, nothing outside them is read.
+ * QUERY: history u of n_hists holds the entries [hist_offsets[u], hist_offsets[u + 1]) of hist_rows [n_hist_items] int32 with the
+ * weights hist_weights (NULL: every weight 1; finite: the host's guarantee).  An entry whose row is outside [0, n_rows) is ABSENT.
+ * The query's ITEMS are its distinct present rows; an item has the weight of its LAST occurrence, and the items are ordered by
+ * the position of that occurrence.  hist_self [n_hists] int32 or NULL: a sequence id never to be used (the user's own training
+ * sequence), or -1.
+ * CANDIDATES: the union is every sequence other than hist_self[u] that holds at least one item; the candidates are its
+ * sample_size LARGEST ids (the most recent possible neighbours).  A candidate s that lies in the posting row of item i lies among
+ * the last sample_size + 1 entries of that row: fewer than sample_size members of the union are larger than s, and the only id
+ * the row can hold beyond them is hist_self.  So only that TAIL of every posting row is read, and what follows is exact.
+ * SIMILARITY: dot(u, s) = the fp32 sum of the weights of the items that s holds, IN ITEM ORDER: the first one assigns, every
+ * later one adds and rounds once.  sim = dot * seq_scale[s], one fp32 multiply; seq_scale [n_seqs] NULL: sim = dot.  (The host
+ * passes 1 / sqrt(|set(s)|) for the cosine; the query's own norm is the same for all of its candidates and is left out.)
+ *   ebn_knn_neighbours_f32: out_seq [n_hists, k] int32 / out_sim [n_hists, k] fp32: the best k candidates of every history, sim
+ *     descending, then id DESCENDING (the more recent one first); -1 / -inf in the slots past the last candidate.  All
+ *     2 n_hists k outputs are written and nothing else.  The order of a NaN sim is not defined (finite weights and scales give
+ *     none).  One 256-thread workgroup per history walks ranges of ebn_knn_range() sequence ids from the most recent downwards
+ *     -- an fp32 sum and a touched bit per id in LDS, the tails cut to the range by two binary searches per item, one barrier
+ *     between items, the next range starting at the largest id a tail still holds -- until sample_size candidates are counted
+ *     from the top; the pairs are sorted in LDS (bitonic).  No floating-point atomics, one fixed order: two runs give the same
+ *     bits.  The last-occurrence scan costs (entries)^2 / 256 compares per history.  A history of at most 256 entries pays it
+ *     ONCE and keeps what it staged (each range then cuts off what it took of a tail); a longer history is staged again, chunk
+ *     by chunk, in EVERY visited range (up to n_seqs / ebn_knn_range() of them), scan and both searches included: meant for
+ *     click histories, not for lists of 10^5 entries.
+ *     n_rows / nnz_p / n_seqs / n_hists / n_hist_items outside [0, 2^31 - 1], sample_size < 1, k < 1, k > sample_size,
+ *     n_hist_items > 0 with n_hists = 0, with n_hists > 0 a NULL hist_offsets / out_seq / out_sim, p_indptr (n_rows > 0), p_seqs
+ *     (nnz_p > 0) or hist_rows (n_hist_items > 0): EBN_ERR_BAD_ARG; then k > EBN_KNN_MAX_K or sample_size > EBN_KNN_MAX_SAMPLE:
+ *     EBN_ERR_UNSUPPORTED; then n_hists == 0: nothing to do (EBN_OK, no launch).  seq_scale, hist_weights and hist_self may be
+ *     NULL; n_rows == 0 or nnz_p == 0 gives -1 / -inf everywhere in one launch.  sample_size > 2048 needs more than 64 KiB of
+ *     LDS: a device that refuses the function attribute for it gives EBN_ERR_UNSUPPORTED, nothing launched.
+ *   ebn_knn_scores_f32: nbr_seq / nbr_sim [n_hists, k] as the call above leaves them.  For item i of list l, c = cand_rows[i],
+ *     u = list_hist ? list_hist[l] : l (lists as for ebn_cv_scores_f32):
+ *       scores[i] = item_scale[c] * sum over the n with 0 <= nbr_seq[u, n] < n_seqs and c in set(nbr_seq[u, n]) of nbr_sim[u, n]
+ *     item_scale [n_rows] NULL: 1.  Exactly +0.0f when the item is absent (c outside [0, n_rows)), u is outside [0, n_hists) or
+ *     history u has no neighbour.  All n_cand_items scores are written and nothing else.  256-item workgroups: one lane per item
+ *     finds its list and history; then one wave per item: lane s takes the neighbours s, s + 64, ..., binary-searches c in the
+ *     neighbour's set and adds the sim at a hit; a butterfly (xor 32 .. 1) folds the lanes.  The order of the sum is the
+ *     kernel's own and fixed; no atomics, no workspace: two runs give the same bits.
+ *     n_seqs / nnz_s / n_rows / n_hists / n_lists / n_cand_items outside [0, 2^31 - 1], k < 1, n_cand_items > 0 with n_lists = 0,
+ *     with n_cand_items > 0 a NULL cand_rows / cand_offsets / scores, s_indptr (n_seqs > 0), s_items (nnz_s > 0) or nbr_seq /
+ *     nbr_sim (n_hists > 0): EBN_ERR_BAD_ARG; then k > EBN_KNN_MAX_K: EBN_ERR_UNSUPPORTED; then n_cand_items == 0: nothing to do
+ *     (EBN_OK, no launch).  item_scale and list_hist may be NULL.
+ * All checked on the host before the launch: a failing call launches and writes nothing.                                          */
+#define EBN_KNN_MAX_K 512
+#define EBN_KNN_MAX_SAMPLE 4096 /* 1 <= k <= sample_size */
+/* The sequence ids one LDS tile of the neighbour kernel covers.  Pure host query.                                                  */
+int64_t ebn_knn_range(void);
+int ebn_knn_neighbours_f32(const int64_t* p_indptr, const int32_t* p_seqs, int64_t n_rows, int64_t nnz_p, int64_t n_seqs,
+                           const float* seq_scale, const int32_t* hist_rows, const float* hist_weights, const int64_t* hist_offsets,
+                           int64_t n_hists, int64_t n_hist_items, const int32_t* hist_self, int32_t sample_size, int32_t k,
+                           int32_t* out_seq, float* out_sim, ebn_stream_t stream);
+int ebn_knn_scores_f32(const int64_t* s_indptr, const int32_t* s_items, int64_t n_seqs, int64_t nnz_s, int64_t n_rows,
+                       const float* item_scale, const int32_t* nbr_seq, const float* nbr_sim, int64_t n_hists, int32_t k,
+                       const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets, int64_t n_lists,
+                       int64_t n_cand_items, float* scores, ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,7 @@ class Problem:
         rng = np.random.default_rng(args.seed)
         self.n_rows = args.rows
         perm = torch.randperm(args.rows, device="cuda", generator=gen)
+        self.perm = perm  # rank -> row: knn_probe.py draws its query histories under the SAME popularity of rows
         h_len = rng.integers(5, 51, args.users)
         self.h_off_np = np.zeros(args.users + 1, np.int64)
         np.cumsum(h_len, out=self.h_off_np[1:])
