@@ -16,7 +16,9 @@ baseline and writes one zipped submission file per baseline into --dump_dir:
     train/history.parquet; each user's validation/history.parquet is folded into the factor space and scored by dot products;
   * knn (with --knn): sequence-neighbourhood collaborative filtering (``HistoryKNN``: the 100 nearest of the 1000 most recent train
     histories that share an article with the user's validation history, cosine, linear history weights, the user's own train
-    history excluded), fitted on train/history.parquet.
+    history excluded), fitted on train/history.parquet;
+  * ease (with --ease): the item-to-item ridge regression EASE^R (``EASE``: regularization --ease_reg, 500 by default, the 16384
+    most-clicked articles), fitted on train/history.parquet and scored against each user's validation/history.parquet.
 
 --topn K adds, for each of covisit and als that is selected, the full-catalogue view (``recommend`` / ``rank_targets``): where the
 clicked article stands among ALL fitted articles under the user's validation history (hit-rate@K, MRR, nDCG@K,
@@ -43,7 +45,7 @@ sys.path.insert(0, str(ROOT / "ebnerd-benchmark_amd"))
 
 from ebrec.evaluation import (AucScore, Coverage, DeviceMetricEvaluator, MetricEvaluator, MrrScore, NdcgScore, Novelty,  # noqa: E402
                               RaggedLists, rank_metrics)
-from ebrec.models import (ArticleFeatureBaseline, CoVisitation, HistoryKNN, ImplicitALS, InviewEstimateBaseline,  # noqa: E402
+from ebrec.models import (EASE, ArticleFeatureBaseline, CoVisitation, HistoryKNN, ImplicitALS, InviewEstimateBaseline,  # noqa: E402
                           PopularityIndex, RecentPopularity, ScoreBlend)
 from ebrec.utils._constants import (DEFAULT_CLICKED_ARTICLES_COL, DEFAULT_HISTORY_ARTICLE_ID_COL,  # noqa: E402
                                     DEFAULT_HISTORY_IMPRESSION_TIMESTAMP_COL, DEFAULT_IMPRESSION_ID_COL, DEFAULT_IMPRESSION_TIMESTAMP_COL,
@@ -66,6 +68,8 @@ def get_args(argv=None):
     ap.add_argument("--covisit", action="store_true", help="add the co-visitation baseline (fit on the train history)")
     ap.add_argument("--als", action="store_true", help="add the implicit-ALS baseline (fit on the train history)")
     ap.add_argument("--knn", action="store_true", help="add the history-kNN baseline (fit on the train history)")
+    ap.add_argument("--ease", action="store_true", help="add the EASE baseline (fit on the train history)")
+    ap.add_argument("--ease_reg", type=float, default=500.0, metavar="R", help="EASE's ridge regularization")
     ap.add_argument("--topn", type=int, default=0, metavar="K", help="also rank the clicked articles among ALL fitted articles and judge the "
                     "top-K lists (covisit / als), 1 to 64")
     ap.add_argument("--blend", action="store_true", help="add a cross-fitted blend of every baseline of the run (5 folds by user)")
@@ -156,6 +160,14 @@ def main(argv=None):
             baselines["knn_prediction_scores"] = lambda frame: knn.predict(frame, history=df_knn_history)
         else:
             skipped["knn_prediction_scores"] = f"history.parquet has no column '{DEFAULT_HISTORY_ARTICLE_ID_COL}'"
+    if args.ease:
+        if DEFAULT_HISTORY_ARTICLE_ID_COL in df_history.columns:
+            ease = EASE(regularization=args.ease_reg, device=device).fit(df_history)
+            df_ease_history = pd.read_parquet(PATH / args.datasplit / "validation" / "history.parquet")
+            print(f"ease: {len(df_history)} sequences of {ease.article_ids.size} articles, regularization {args.ease_reg:g}")
+            baselines["ease_prediction_scores"] = lambda frame: ease.predict(frame, history=df_ease_history)
+        else:
+            skipped["ease_prediction_scores"] = f"history.parquet has no column '{DEFAULT_HISTORY_ARTICLE_ID_COL}'"
     for name, why in skipped.items():
         print(f"skipped {name}: {why}")
 

@@ -1674,6 +1674,82 @@ int ebn_knn_scores_f32(const int64_t* s_indptr, const int32_t* s_items, int64_t 
                        const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets, int64_t n_lists,
                        int64_t n_cand_items, float* scores, ebn_stream_t stream);
 
+/* ---- EASE^R baseline (Steck, "Embarrassingly Shallow Autoencoders for Sparse Data", WWW 2019): the item-to-item ridge regression in
+ * closed form (the reference has no such baseline; the float64 brute force of tests/ease_cases.py is the yardstick; host layer:
+ * ebrec/models/baselines/ease.py; kernels: csrc/ebn_ease.hip) ---------------------------------------------------------------------
+ * With X [users, n] binary (item i occurs in user u's sequence):  G = X^T X (co-click counts, item counts on the diagonal),
+ * A = G + reg I,  P = A^{-1},  B[i, j] = -P[i, j] / P[j, j] for i != j, B[j, j] = 0.  The score of candidate c for a history
+ * h_1 .. h_m with weights w is sum_j w_j B[h_j, c] (x^T B: B is not symmetric).  One entry point per stage:
+ *   ebn_ease_gram_i32: CSR over n_users rows: row u holds the entries [indptr[u], indptr[u + 1]) clamped to [0, nnz] of cols [nnz]
+ *     int32, taken AS GIVEN (the host layer makes them ascending and distinct; a repeated column counts as often as it pairs); an
+ *     entry outside [0, n_items) is skipped and never turned into an address.  G int32 [n_items, ldg]: the call zeroes the LOWER
+ *     triangle (j <= i) itself, then adds 1 to G[max(a, b), min(a, b)] for every pair of positions p >= q of a row whose columns
+ *     a, b are present, with INTEGER global atomics: integer sums commute, two runs give the same bits.  The upper triangle and the
+ *     columns >= n_items are never written.  One 256-thread workgroup per row; a row of m entries costs m (m + 1) / 2 atomics
+ *     spread over its threads; m is not capped.
+ *     n_users / nnz / n_items / ldg outside [0, 2^31 - 1], ldg < n_items, a NULL G (n_items > 0), indptr (n_users > 0) or cols
+ *     (nnz > 0): EBN_ERR_BAD_ARG; then n_items > EBN_EASE_MAX_ITEMS: EBN_ERR_UNSUPPORTED; then n_items == 0: nothing to do (EBN_OK,
+ *     no launch).  n_users == 0 or nnz == 0: zeros in one launch.
+ *   ebn_ease_system_f32: A[i, j] = A[j, i] = (float) G[max(i, j), min(i, j)] for i, j < n, plus reg on the diagonal (one fp32 add);
+ *     only the lower triangle of G is read, only columns < n of A are written.  *flag (device int32, only ever SET: the caller
+ *     zeroes it) becomes 1 when a count read exceeds 2^24, where it is no longer exact in fp32.
+ *     n / ldg / lda outside [0, 2^31 - 1], ldg < n, lda < n, reg not finite, with n > 0 a NULL G / A / flag: EBN_ERR_BAD_ARG; then
+ *     n > EBN_EASE_MAX_ITEMS: EBN_ERR_UNSUPPORTED; then n == 0: EBN_OK, no launch.
+ *   ebn_ease_invert_f32: A [n, n] at row stride lda, symmetric positive definite (only its lower triangle is read), is overwritten
+ *     by the full symmetric A^{-1}: (i, j) and (j, i) hold the same bits; columns >= n are never read or written.  A host loop of
+ *     launches on `stream`, no synchronisation and no host read in between: (1) blocked right-looking Cholesky with block size
+ *     NB = ebn_ease_block(): a one-workgroup kernel factorises the NB x NB diagonal block in LDS (fixed order, correctly rounded
+ *     sqrtf and division) and inverts its triangular factor in the same launch, W_k = L_kk^{-1}; the panel below, L_ik = A_ik W_k^T,
+ *     and the trailing update A_22 -= L_21 L_21^T (column strips starting at the diagonal) run on ebn_gemm_f32; (2) Z = L^{-1} by
+ *     block forward substitution with the same W_k and GEMMs; (3) P = Z^T Z by GEMMs over column strips, then mirrored.  No
+ *     floating-point atomics and no split-K: two runs give the same bits.  n need not be a multiple of NB.
+ *     info (device int32) is WRITTEN: 0 = ok, k + 1 = the first pivot (global index k) that was not > 0, NaN included.  After such
+ *     a pivot the remaining launches still run and A holds NaN-filled garbage; nothing faults and nothing waits for the host (the
+ *     host layer raises FloatingPointError).  work: ebn_ease_workspace_floats(n) floats, written before they are read; 16-byte
+ *     alignment of A / work and lda % 4 == 0, n % 4 == 0 let the GEMMs use their vector loads (the bits then depend on it, as
+ *     ebn_gemm_f32's do).
+ *     n / lda outside [0, 2^31 - 1], lda < n, a NULL A / work / info: EBN_ERR_BAD_ARG; then n > EBN_EASE_MAX_ITEMS or work_floats
+ *     below the query: EBN_ERR_UNSUPPORTED; then n == 0: EBN_OK, no launch.
+ *   ebn_ease_invert_nb_f32: the same with the block size given, nb in {32, 64, 128} (else EBN_ERR_BAD_ARG, with the first group):
+ *     the measurement hook behind the choice of ebn_ease_block() (tools/ease_probe.py).  The workspace query covers every nb.
+ *   ebn_ease_weights_f32: B[i, j] = -(P[i, j] / P[j, j]) for i != j (correctly rounded division), exact +0.0 on the diagonal;
+ *     n * n elements are written and nothing else.  B == P (in place) is allowed: the first launch writes the off-diagonal
+ *     elements and only reads the diagonal, the second writes the diagonal.
+ *     n / ldp / ldb outside [0, 2^31 - 1], ldp < n, ldb < n, with n > 0 a NULL P / B: EBN_ERR_BAD_ARG; then
+ *     n > EBN_EASE_MAX_ITEMS: EBN_ERR_UNSUPPORTED; then n == 0: EBN_OK, no launch.
+ *   ebn_ease_scores_f32: B [n_items, ldb] fp32; histories and lists as for ebn_cv_scores_f32 (hist_rows / hist_weights /
+ *     hist_offsets, list_hist, cand_rows / cand_offsets; extents clamped to [0, n_hist_items]; an entry or item whose row is
+ *     outside [0, n_items) is ABSENT; an entry that occurs twice counts twice).  For item i of list l, c = cand_rows[i],
+ *     u = list_hist ? list_hist[l] : l:
+ *       scores[i] = sum over the present entries j of history u of w_j * B[hist_rows[j], c]          (w_j = 1 with hist_weights NULL)
+ *     exactly +0.0f when the item is absent, u is outside [0, n_hists) or history u has no present entry.  All n_cand_items scores
+ *     are written and nothing else.  256-item workgroups: one lane per item finds its list and history; then one wave per item:
+ *     lane s takes the entries s, s + 64, ... in order (one fused multiply-add each; a plain add without weights), a butterfly
+ *     (xor 32 .. 1) folds the lanes.  The order is fixed, no atomics, no workspace: two runs give the same bits.
+ *     n_items / ldb / n_hists / n_hist_items / n_lists / n_cand_items outside [0, 2^31 - 1], ldb < n_items, n_cand_items > 0 with
+ *     n_lists = 0, n_hist_items > 0 with n_hists = 0: EBN_ERR_BAD_ARG; then n_cand_items == 0: nothing to do (EBN_OK, no launch);
+ *     then a NULL cand_rows / cand_offsets / scores, B (n_items > 0), hist_offsets (n_hists > 0) or hist_rows (n_hist_items > 0):
+ *     EBN_ERR_BAD_ARG.  hist_weights and list_hist may be NULL.
+ * All checked on the host before the launch: a failing call launches and writes nothing.                                          */
+#define EBN_EASE_MAX_ITEMS 32768
+/* The block size NB of ebn_ease_invert_f32.  Pure host query.                                                                      */
+int ebn_ease_block(void);
+/* Floats of workspace for ebn_ease_invert_f32 / ebn_ease_invert_nb_f32 (about n^2 + 256 n); 0 for n outside [0, EBN_EASE_MAX_ITEMS].
+ * Pure host query.                                                                                                                 */
+int64_t ebn_ease_workspace_floats(int64_t n);
+int ebn_ease_gram_i32(const int64_t* indptr, const int32_t* cols, int64_t n_users, int64_t nnz, int64_t n_items, int32_t* G,
+                      int64_t ldg, ebn_stream_t stream);
+int ebn_ease_system_f32(const int32_t* G, int64_t ldg, int64_t n, float reg, float* A, int64_t lda, int32_t* flag,
+                        ebn_stream_t stream);
+int ebn_ease_invert_f32(float* A, int64_t lda, int64_t n, float* work, int64_t work_floats, int32_t* info, ebn_stream_t stream);
+int ebn_ease_invert_nb_f32(float* A, int64_t lda, int64_t n, float* work, int64_t work_floats, int32_t* info, int32_t nb,
+                           ebn_stream_t stream);
+int ebn_ease_weights_f32(const float* P, int64_t ldp, int64_t n, float* B, int64_t ldb, ebn_stream_t stream);
+int ebn_ease_scores_f32(const float* B, int64_t n_items, int64_t ldb, const int32_t* hist_rows, const float* hist_weights,
+                        const int64_t* hist_offsets, int64_t n_hists, int64_t n_hist_items, const int32_t* list_hist,
+                        const int32_t* cand_rows, const int64_t* cand_offsets, int64_t n_lists, int64_t n_cand_items, float* scores,
+                        ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
