@@ -49,30 +49,6 @@ struct CvRankArgs : CvTileArgs {
 inline int64_t cv_topk_lds_bytes() { return static_cast<int64_t>(CVT_TILE_FLOATS + CVK_MERGE_FLOATS) * 4; }
 inline int64_t cv_rank_lds_bytes() { return static_cast<int64_t>(CVT_TILE_FLOATS + CVR_OWN_FLOATS) * 4; }
 
-// the whole wave inserts (ns, np) into its list: lane t holds slot t in (es, ep)
-__device__ __forceinline__ void cvk_insert(float& es, int& ep, int k, int lane, float ns, int np) {
-  const bool in = lane < k;
-  const int rank = __popcll(__ballot(in && topk_before(es, ep, ns, np)));
-  const float us = __shfl_up(es, 1, 64);
-  const int up = __shfl_up(ep, 1, 64);
-  if (in && lane >= rank) {  // rank == k: nobody
-    es = lane == rank ? ns : us;
-    ep = lane == rank ? np : up;
-  }
-}
-
-// the lanes with ok offer (s, pos); what ranks before the list's k-th entry goes in
-__device__ __forceinline__ void cvk_offer(float& es, int& ep, int k, int lane, bool ok, float s, int pos) {
-  const float ks = __shfl(es, k - 1, 64);
-  const int kp = __shfl(ep, k - 1, 64);
-  unsigned long long m = __ballot(ok && topk_before(s, pos, ks, kp));
-  while (m != 0ull) {
-    const int src = __builtin_ctzll(m);
-    m &= m - 1ull;
-    cvk_insert(es, ep, k, lane, __shfl(s, src, 64), __shfl(pos, src, 64));
-  }
-}
-
 template <bool MAX>
 __global__ __launch_bounds__(CVT_THREADS, 2) void cv_topk_kernel(CvTopkArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -104,7 +80,7 @@ __global__ __launch_bounds__(CVT_THREADS, 2) void cv_topk_kernel(CvTopkArgs a) {
         int pos = 0;
         float s = 0.f;
         const bool ok = c < n && cvt_admissible(a, t, r0, c, wlo, whi, pos, s, oob, nan);
-        if (__ballot(ok) != 0ull) cvk_offer(es, ep, k, lane, ok, s, pos);
+        if (__ballot(ok) != 0ull) topk_wave_offer(es, ep, k, lane, ok, s, pos);
       }
     }
   }
@@ -121,7 +97,7 @@ __global__ __launch_bounds__(CVT_THREADS, 2) void cv_topk_kernel(CvTopkArgs a) {
   for (int w = 0; w < 3; ++w) {
     const float s = lane < k ? ms[w * 64 + lane] : 0.f;
     const int pos = lane < k ? mp[w * 64 + lane] : TK_EMPTY;
-    cvk_offer(es, ep, k, lane, pos != TK_EMPTY, s, pos);
+    topk_wave_offer(es, ep, k, lane, pos != TK_EMPTY, s, pos);
   }
   if (lane < k) {
     if (a.n_splits == 1) {

@@ -123,6 +123,32 @@ __device__ __forceinline__ void topk_list_drain(const TopkList& a, const TopkLds
   }
 }
 
+// ---- a wave-private list in REGISTERS (ebn_covisit_topk.hip, ebn_ease_topk.hip): lane t holds slot t of the sorted list of k <= 64
+// entries; the same insertion as topk_list_drain's without the LDS round trip
+// the whole wave inserts (ns, np) into its list: lane t holds slot t in (es, ep)
+__device__ __forceinline__ void topk_wave_insert(float& es, int& ep, int k, int lane, float ns, int np) {
+  const bool in = lane < k;
+  const int rank = __popcll(__ballot(in && topk_before(es, ep, ns, np)));
+  const float us = __shfl_up(es, 1, 64);
+  const int up = __shfl_up(ep, 1, 64);
+  if (in && lane >= rank) {  // rank == k: nobody
+    es = lane == rank ? ns : us;
+    ep = lane == rank ? np : up;
+  }
+}
+
+// the lanes with ok offer (s, pos); what ranks before the list's k-th entry goes in
+__device__ __forceinline__ void topk_wave_offer(float& es, int& ep, int k, int lane, bool ok, float s, int pos) {
+  const float ks = __shfl(es, k - 1, 64);
+  const int kp = __shfl(ep, k - 1, 64);
+  unsigned long long m = __ballot(ok && topk_before(s, pos, ks, kp));
+  while (m != 0ull) {
+    const int src = __builtin_ctzll(m);
+    m &= m - 1ull;
+    topk_wave_insert(es, ep, k, lane, __shfl(s, src, 64), __shfl(pos, src, 64));
+  }
+}
+
 // a wave writes the lists of its own 32 rows: lane t slot t; one split writes the outputs, more write their partial lists
 __device__ __forceinline__ void topk_list_write(const TopkList& a, const TopkLds& l, int64_t u0, int split, int wave, int lane) {
   const int k = a.k;

@@ -5,7 +5,7 @@ counterpart of the neural models' ``recommend`` / ``rank_targets`` (ebrec/models
     ranks = cv.rank_targets(df_validation, history=df_history_validation)                # the clicked article among ALL articles
     rank_metrics(ranks.rank, ks=(5, 10), counts=ranks.count)                             # hit-rate@k, MRR, nDCG@k
 
-``TopN`` is the host scaffolding ``CoVisitation``, ``ImplicitALS`` and ``ContentSimilarity`` share: the three call forms, the
+``TopN`` is the host scaffolding ``CoVisitation``, ``ImplicitALS``, ``ContentSimilarity`` and ``EASE`` share: the three call forms, the
 candidate list, history exclusion, freshness windows, batching, the id mapping and the flags.  A class takes part by offering
 
     _topn_ids()                    -> the sorted article ids that name the catalogue rows
@@ -17,11 +17,11 @@ candidate list, history exclusion, freshness windows, batching, the id mapping a
 
 with numpy arguments; the results are numpy on the host path and device tensors on the device path, ``flags`` [2] likewise.  Row
 b of a launch uses history ``hist_idx[b]`` (-1: none).  Co-visitation's session launches ``ebn_cv_topk_f32`` /
-``ebn_cv_target_rank_f32`` (covisit.py); ``DenseSession`` below serves the two classes whose users are dense vectors -- ALS fold-in
+``ebn_cv_target_rank_f32`` (covisit.py), EASE's ``ebn_ease_topk_f32`` / ``ebn_ease_target_rank_f32`` (ease.py); ``DenseSession`` below serves the two classes whose users are dense vectors -- ALS fold-in
 rows, content-centroid profiles -- with the EXISTING ``ebn_topk_score_f32`` / ``ebn_topk_score_window_f32`` / ``ebn_target_rank_f32``
 (columns zero-padded to a multiple of 4), and with float64 numpy twins on the host.
 
-Out of scope: nearest-history top-N, the popularity baselines, re-rankers on baseline lists."""
+Out of scope: nearest-history top-N, the popularity baselines, re-rankers on baseline lists (DESIGN.md sections 31 and 35)."""
 from __future__ import annotations
 
 import numpy as np

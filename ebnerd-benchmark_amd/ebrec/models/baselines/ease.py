@@ -24,8 +24,15 @@ use their vector loads), ``ebn_ease_weights_f32`` in place, ``ebn_ease_scores_f3
 runs the numpy twins ``ease_gram_host`` / ``ease_system_host`` / ``ease_invert_host`` / ``ease_weights_host`` / ``ease_scores_host``:
 the same contracts in float64 on the float32 / integer operands, rounded once to float32 where the kernel stores float32.  A pivot
 that is not > 0 raises FloatingPointError on both paths, a co-click count above 2^24 OverflowError.
-Not here: ``recommend`` / ``rank_targets`` (a history's score row is a sum of rows of B and wants a kernel of its own), weighted X,
-catalogues above 32768 items, several GPUs.  numpy / pandas on the host; torch is imported only on the device path."""
+TOP-N.  ``recommend`` / ``rank_targets`` (``TopN``, _topn.py) are the second outlet: each impression's best ``top_n`` of ALL fitted
+articles, and the full-catalogue rank of its clicked article, under history exclusion and freshness windows.  B is dense, so every
+article has a score for a user with at least one known history article (negative ones included), and a user without one gets an
+empty list.  On the device they run ``ebn_ease_topk_f32`` / ``ebn_ease_target_rank_f32`` (csrc/ebn_ease_topk.hip): a history's score
+row is the sum of its rows of B, kept in registers.  The numpy twins ``ease_topk_host`` / ``ease_target_rank_host`` do the same
+float32 chain in history order, vectorised over the columns, and are bit-equal to the kernels.  That chain is not the summation
+order of ``ebn_ease_scores_f32``: ``return_scores`` and ``predict`` agree to rounding, not in bits.
+Not here: weighted X, catalogues above 32768 items, several GPUs, a max mode.  numpy / pandas on the host; torch is imported only on
+the device path."""
 from __future__ import annotations
 
 import numpy as np
@@ -33,6 +40,7 @@ import numpy as np
 from ebrec.evaluation.device_metrics import RaggedLists, device_available
 from ebrec.utils._constants import DEFAULT_HISTORY_ARTICLE_ID_COL
 
+from ._topn import TopN
 from .als import _combine_device, _combine_host
 from .content import ContentSimilarity, _keep_last, _list_histories, _present_entries, history_operands
 from .popularity import _explode, _frame, _ragged_ids, _rows_of
@@ -158,6 +166,119 @@ def ease_scores_host(B, hist_rows, hist_weights, hist_offsets, list_hist, cand_r
     return out
 
 
+# ---- top-N over the whole catalogue: the numpy twins of ebn_ease_topk_f32 / ebn_ease_target_rank_f32 -----------------------------
+MAX_TOP_K, MAX_EXCLUDE = 64, 256  # limits of include/ebnerd_hip.h
+
+
+def ease_chain_host(B, rows, weights):
+    """one history's scores over the whole catalogue in the kernel's arithmetic -> (scored: bool, score [n_rows] float32): the
+    present entries in history order, the first product stored, the later ones added; every product and every add rounds once to
+    float32, vectorised over the columns"""
+    n_rows = B.shape[0]
+    score, scored = np.zeros(n_rows, np.float32), False
+    with np.errstate(all="ignore"):
+        for j, h in enumerate(np.asarray(rows).tolist()):
+            if not 0 <= h < n_rows:
+                continue
+            p = B[h, :n_rows] if weights is None else np.float32(weights[j]) * B[h, :n_rows]
+            score = (score + p if scored else p).astype(np.float32)
+            scored = True
+    return scored, score
+
+
+def ease_chains_host(B, hist_rows, hist_weights, hist_offsets) -> list:
+    """[(scored, score [n_rows] float32)] per history: the part of the twins that depends on neither the candidates nor the windows
+    nor the exclusion lists (``chains=`` of both twins takes it, so that several calls share it)"""
+    B = np.asarray(B, np.float32)
+    hist_rows, hist_offsets = np.asarray(hist_rows, np.int64).ravel(), np.asarray(hist_offsets, np.int64).ravel()
+    w_all = None if hist_weights is None else np.asarray(hist_weights, np.float32).ravel()
+    out = []
+    for h in range(hist_offsets.size - 1):
+        a, b = (min(max(int(v), 0), hist_rows.size) for v in (hist_offsets[h], hist_offsets[h + 1]))
+        out.append(ease_chain_host(B, hist_rows[a:b], None if w_all is None else w_all[a:b]))
+    return out
+
+
+def _ease_walk_host(B, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window, exclude, chains=None):
+    """per user: (admissible columns, their positions, the float32 scores of all columns, flags)"""
+    B = np.asarray(B, np.float32)
+    if B.ndim != 2 or B.shape[1] < B.shape[0]:
+        raise ValueError("B must be [n, ld] with ld >= n")
+    n_rows = B.shape[0]
+    hist_rows, hist_offsets = np.asarray(hist_rows, np.int64).ravel(), np.asarray(hist_offsets, np.int64).ravel()
+    w_all = None if hist_weights is None else np.asarray(hist_weights, np.float32).ravel()
+    n_hists = hist_offsets.size - 1
+    pos_of = np.arange(n_rows, dtype=np.int64) if cand_pos is None else np.asarray(cand_pos, np.int64).ravel()
+    if pos_of.size != n_rows or (cand_pos is None and M != n_rows):
+        raise ValueError(f"cand_pos must hold one position per catalogue row ({n_rows}); without it M == n_rows")
+    flags = np.zeros(2, np.int32)
+    beyond, none = bool((pos_of >= M).any()), (False, np.zeros(n_rows, np.float32))
+    memo = {}
+    for u in range(int(n_users)):
+        h = u if user_hist is None else int(user_hist[u])
+        scored, score = none
+        if 0 <= h < n_hists:
+            if chains is not None:
+                scored, score = chains[h]
+            else:
+                if h not in memo:
+                    if len(memo) >= 64:
+                        memo.clear()
+                    a, b = (min(max(int(v), 0), hist_rows.size) for v in (hist_offsets[h], hist_offsets[h + 1]))
+                    memo[h] = ease_chain_host(B, hist_rows[a:b], None if w_all is None else w_all[a:b])
+                scored, score = memo[h]
+        lo, hi = 0, int(M)
+        if window is not None:
+            lo, hi = max(int(window[u][0]), 0), min(int(window[u][1]), int(M))
+            if lo >= hi:
+                lo = hi = 0
+        if scored and beyond:
+            flags[0] = 1
+        adm = np.full(n_rows, scored) & (pos_of >= lo) & (pos_of < hi)
+        if exclude is not None:
+            ex = np.asarray(exclude[u], np.int64).ravel()
+            adm[ex[(ex >= 0) & (ex < n_rows)]] = False
+        if (adm & np.isnan(score)).any():
+            flags[1] = 1
+        adm &= ~np.isnan(score)
+        cols = np.flatnonzero(adm)
+        yield u, cols, pos_of[cols], score, flags
+
+
+def ease_topk_host(B, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window, exclude, k, chains=None):
+    """numpy twin of ebn_ease_topk_f32, bit-equal to it -> (pos [U, k] int32, score [U, k] float32, flags [2] int32)"""
+    if not 1 <= int(k) <= MAX_TOP_K:
+        raise ValueError(f"k must lie in [1, {MAX_TOP_K}], got {k}")
+    out_pos, out_score = np.full((int(n_users), int(k)), -1, np.int32), np.full((int(n_users), int(k)), -np.inf, np.float32)
+    flags = np.zeros(2, np.int32)
+    for u, cols, pos, score, flags in _ease_walk_host(B, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window,
+                                                      exclude, chains):
+        s = score[cols]
+        best = np.lexsort((pos, -s))[:int(k)]  # score descending, then position ascending
+        out_pos[u, :best.size], out_score[u, :best.size] = pos[best], s[best]
+    return out_pos, out_score, flags
+
+
+def ease_target_rank_host(B, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, target_pos, window, exclude,
+                          chains=None):
+    """numpy twin of ebn_ease_target_rank_f32 -> (rank [U] int32, count [U] int32, score [U] float32, flags [2] int32)"""
+    target_pos = np.asarray(target_pos, np.int64).ravel()
+    U = int(n_users)
+    rank, count, t_out = np.zeros(U, np.int32), np.zeros(U, np.int32), np.full(U, -np.inf, np.float32)
+    flags, oob_target = np.zeros(2, np.int32), bool((target_pos[:U] >= M).any())
+    for u, cols, pos, score, flags in _ease_walk_host(B, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window,
+                                                      exclude, chains):
+        count[u] = cols.size
+        at = np.flatnonzero(pos == target_pos[u]) if 0 <= target_pos[u] < M else np.zeros(0, np.int64)
+        if at.size:
+            s, t = score[cols], score[cols[at[0]]]
+            rank[u] = 1 + int(((s > t) | ((s == t) & (pos < target_pos[u]))).sum())
+            t_out[u] = t
+    if oob_target:
+        flags[0] = 1
+    return rank, count, t_out, flags
+
+
 # ---- the launches ----------------------------------------------------------------------------------------------------------------
 def _pad4(n: int) -> int:
     return (n + 3) // 4 * 4
@@ -217,8 +338,132 @@ def scores_call(B, hist_rows, hist_weights, hist_offsets, list_hist, cand_rows, 
     return scores
 
 
+def _ease_operands(B, hist_rows, hist_weights, hist_offsets, user_hist, cand_pos, M):
+    from ebrec import _hip
+
+    n_rows = B.shape[0]
+    if B.dim() != 2 or B.stride(1) != 1 or B.stride(0) < n_rows:
+        raise ValueError("B must be a [n, n] float32 tensor with unit column stride")
+    M = n_rows if cand_pos is None else int(M)
+    return (_hip.ptr(B), n_rows, max(B.stride(0), n_rows), _hip.ptr(hist_rows), _hip.ptr(hist_weights),
+            _hip.ptr(hist_offsets), hist_offsets.numel() - 1, hist_rows.numel(), _hip.ptr(user_hist), _hip.ptr(cand_pos), M), n_rows
+
+
+def _check_device_args(U, window, exclude, target_pos=None):
+    import torch
+
+    for name, t, shape in (("window", window, (U, 2)), ("exclude", exclude, None), ("target_pos", target_pos, (U,))):
+        if t is None:
+            continue
+        if t.dtype != torch.int32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape) or \
+                (shape is None and (t.dim() != 2 or t.shape[0] != U)):
+            raise ValueError(f"{name} must be a contiguous int32 tensor with one row per user ({U}), got {tuple(t.shape)} {t.dtype}")
+
+
+def topk_call(B, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, window, exclude, k, flags, n_splits: int = 0):
+    """One ebn_ease_topk_f32 launch over device tensors (``hist_weights`` / ``user_hist`` / ``cand_pos`` / ``window`` [U, 2] /
+    ``exclude`` [U, X] may be None; B at any row stride) -> (pos [U, k] int32, score [U, k] float32); ``flags`` [2] int32
+    accumulates."""
+    import torch
+
+    from ebrec import _hip
+
+    U, dev = int(n_users), B.device
+    _check_device_args(U, window, exclude)
+    ops, n_rows = _ease_operands(B, hist_rows, hist_weights, hist_offsets, user_hist, cand_pos, M)
+    pos = torch.empty(U, k, dtype=torch.int32, device=dev)
+    score = torch.empty(U, k, dtype=torch.float32, device=dev)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_ease_topk_auto_splits(U, n_rows))
+    ws = torch.empty(max(int(lib.ebn_ease_topk_workspace_bytes(U, k, max(splits, 1))), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("ebn_ease_topk_f32", *ops, _hip.ptr(window), _hip.ptr(exclude), 0 if exclude is None else exclude.shape[1], int(k), splits,
+                  _hip.ptr(pos), _hip.ptr(score), _hip.ptr(flags), _hip.ptr(ws), ws.numel(), U, _hip.stream_handle())
+    return pos, score
+
+
+def rank_call(B, hist_rows, hist_weights, hist_offsets, user_hist, n_users, cand_pos, M, target_pos, window, exclude, flags,
+              n_splits: int = 0):
+    """One ebn_ease_target_rank_f32 launch over device tensors: ``target_pos`` [U] int32 candidate positions (< 0: none) -> (rank [U]
+    int32: 1-based place in ``topk_call``'s order, 0 = not ranked; count [U] int32: the user's admissible columns; score [U]
+    float32: the target's score, -inf where rank is 0); ``flags`` accumulates."""
+    import torch
+
+    from ebrec import _hip
+
+    U, dev = int(n_users), B.device
+    _check_device_args(U, window, exclude, target_pos)
+    ops, n_rows = _ease_operands(B, hist_rows, hist_weights, hist_offsets, user_hist, cand_pos, M)
+    rank = torch.empty(U, dtype=torch.int32, device=dev)
+    count = torch.empty(U, dtype=torch.int32, device=dev)
+    score = torch.empty(U, dtype=torch.float32, device=dev)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_ease_topk_auto_splits(U, n_rows))
+    ws = torch.empty(max(int(lib.ebn_ease_target_rank_workspace_bytes(U, max(splits, 1), 0 if cand_pos is None else int(M))), 16),
+                     dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("ebn_ease_target_rank_f32", *ops, _hip.ptr(target_pos), _hip.ptr(window), _hip.ptr(exclude),
+                  0 if exclude is None else exclude.shape[1], splits, _hip.ptr(rank), _hip.ptr(count), _hip.ptr(score), _hip.ptr(flags),
+                  _hip.ptr(ws), ws.numel(), U, _hip.stream_handle())
+    return rank, count, score
+
+
+class EaseSession:
+    """what ``TopN`` drives (see _topn.py): the histories of one ``recommend`` / ``rank_targets`` call against B; device tensors and
+    the two kernels when B lives on the device, the float32 twins otherwise"""
+
+    def __init__(self, B, h_rows, h_off, w, on_device: bool):
+        self.on_device, self.B, self.n_rows = on_device, B, int(B.shape[0])
+        self.cand_pos, self.M = None, self.n_rows
+        self.device = B.device if on_device else None
+        if on_device:
+            import torch
+
+            up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            self.hist = (up(h_rows.astype(np.int32)), up(w), up(np.ascontiguousarray(h_off, dtype=np.int64)))
+        else:
+            self.hist = (h_rows, w, np.ascontiguousarray(h_off, dtype=np.int64))
+
+    def candidates(self, cand_rows):
+        """position -> row becomes the kernels' row -> position (-1: no candidate); the identity is passed as None"""
+        rows = np.asarray(cand_rows, np.int64)
+        self.M = rows.size
+        if rows.size == self.n_rows and np.array_equal(rows, np.arange(self.n_rows)):
+            self.cand_pos = None
+            return
+        pos = np.full(self.n_rows, -1, np.int32)
+        pos[rows] = np.arange(rows.size, dtype=np.int32)
+        self.cand_pos = pos
+        if self.on_device:
+            import torch
+
+            self.cand_pos = torch.from_numpy(pos).to(self.device)
+
+    def _up(self, a):
+        import torch
+
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    def topk(self, hist_idx, window, exclude, k, flags):
+        U = len(hist_idx)
+        if not self.on_device:
+            pos, score, f = ease_topk_host(self.B, *self.hist, hist_idx, U, self.cand_pos, self.M, window, exclude, k)
+            flags |= f
+            return pos, score
+        return topk_call(self.B, *self.hist, self._up(hist_idx), U, self.cand_pos, self.M, self._up(window), self._up(exclude), k, flags)
+
+    def rank(self, hist_idx, target_pos, window, exclude, flags):
+        U = len(hist_idx)
+        if not self.on_device:
+            rank, count, score, f = ease_target_rank_host(self.B, *self.hist, hist_idx, U, self.cand_pos, self.M, target_pos, window, exclude)
+            flags |= f
+            return rank, count, score
+        return rank_call(self.B, *self.hist, self._up(hist_idx), U, self.cand_pos, self.M, self._up(target_pos), self._up(window),
+                         self._up(exclude), flags)
+
+
 # ---- the class -----------------------------------------------------------------------------------------------------------------
-class EASE:
+class EASE(TopN):
     """EASE^R.  ``regularization``: reg > 0 (as a float32); ``max_items``: the most-clicked articles kept, at most 32768;
     ``history_size`` / ``history_weights`` / ``lambda_factor`` / ``fill``: as in ``ContentSimilarity`` (``history_size`` also cuts the
     training sequences; the training matrix is binary whatever the weights).  After ``fit``: ``article_ids`` (sorted, numpy),
@@ -294,7 +539,7 @@ class EASE:
     @classmethod
     def from_weights(cls, article_ids, B, **kw) -> "EASE":
         """a fitted model from a given matrix B [n, n] (rows and columns in the order of ``article_ids``: any order, no repeats):
-        ``predict`` and ``similar_items`` work; ``item_counts`` stays None"""
+        ``predict``, ``recommend``, ``rank_targets`` and ``similar_items`` work; ``item_counts`` stays None"""
         ids = np.asarray(article_ids).ravel()
         B = np.asarray(B.cpu().numpy() if hasattr(B, "cpu") else B, np.float32)
         if B.ndim != 2 or B.shape != (ids.size, ids.size) or np.unique(ids).size != ids.size:
@@ -329,6 +574,21 @@ class EASE:
     def _histories(self, histories):
         """ids of histories -> (rows int32, offsets int64, weights float32 | None)"""
         return history_operands(self.rows_of, histories, self.history_size, self.history_weights, self.lambda_factor)
+
+    # -- recommend / rank_targets (TopN, _topn.py): ebn_ease_topk_f32 / ebn_ease_target_rank_f32 over B.  Every article has a score
+    # for a user with a known history article; a user without one gets an empty list and rank 0
+    def _topn_ids(self):
+        self._fitted()
+        return self.article_ids
+
+    def _topn_rows_of(self, ids):
+        return self.rows_of(ids)
+
+    def _topn_session(self, histories):
+        B = self._fitted()
+        h_rows, h_off, w = self._histories(histories)
+        on_device = not isinstance(B, np.ndarray) and device_available(self.device)
+        return EaseSession(B if on_device else self.host_weights(), h_rows, h_off, w, on_device)
 
     # -- public
     def predict(self, candidates, histories=None, list_hist=None, *, history=None) -> RaggedLists:

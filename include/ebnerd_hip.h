@@ -1750,6 +1750,67 @@ int ebn_ease_scores_f32(const float* B, int64_t n_items, int64_t ldb, const int3
                         const int32_t* cand_rows, const int64_t* cand_offsets, int64_t n_lists, int64_t n_cand_items, float* scores,
                         ebn_stream_t stream);
 
+/* ---- EASE top-N lists and clicked-article ranks over the whole catalogue (csrc/ebn_ease_topk.hip; the plain-Python brute force of
+ * tests/ease_topn_cases.py is the yardstick): what ebn_cv_topk_f32 and ebn_cv_target_rank_f32 are to the co-visitation matrix, for
+ * the DENSE row sums of EASE -------------------------------------------------------------------------------------------------------
+ * Everything not said here is ebn_cv_topk_f32's / ebn_cv_target_rank_f32's: the history operands and their clamping to
+ * [0, n_hist_items], ABSENT entries (a row outside [0, n_rows): it adds nothing and is never turned into an address), a repeated
+ * entry counting twice, user_hist, cand_pos [n_rows] (negative: no candidate; NULL: position = row, then M == n_rows; >= M: skipped
+ * and flags[0] set), window [U, 2] and exclude [U, X] by catalogue row, the total order (score descending, then position
+ * ascending) with -1 / -inf in the empty trailing slots, flags [2] only ever SET, the outputs of the rank call, the workspace
+ * rules, all argument checks on the host before anything is launched: a failing call writes nothing.
+ * MATRIX: B [n_rows, ldb] fp32, row-major, any ldb >= n_rows and any alignment: the weights of ebn_ease_weights_f32.  Only the
+ * columns < n_rows of a row are read.
+ * SCORE: column c is scored for user u when u's history has at least one present entry -- B is dense, there is no "touched"
+ * notion: every column of such a user has a score, a user without a present entry has none (an empty list; rank 0, count 0,
+ * score -inf).  With p_j = w_j * B[hist_rows[j], c] (hist_weights NULL: the stored value itself): the score starts as the first
+ * present entry's p_j; every later present entry, in history order, does acc = acc + p_j.  Every product and every add rounds
+ * once to fp32 (no fused multiply-add).  A score's bits depend on that user's history and that column of B only: not on U, M,
+ * n_splits, ldb, the alignment of B (16-byte loads or 4-byte loads: the same operations), the run or the other users of the
+ * launch.  No floating-point atomics.  This chain is NOT the lane-strided fma order of ebn_ease_scores_f32: predict and recommend
+ * agree to rounding (two fp32 summation orders of the same rounded products), not in bits.
+ * ADMISSIBLE: column c for user u when it is scored, cand_pos[c] lies in [0, M) and in u's clamped window, c is not in
+ * exclude[u, :] and the score is not NaN.  A NaN score that is admissible otherwise sets flags[1]; +-inf rank like numbers.  A
+ * position >= M sets flags[0] when some user with a present entry walks the column.
+ *   ebn_ease_topk_f32: out_pos [U, k] / out_score [U, k], 1 <= k <= 64.
+ *   ebn_ease_target_rank_f32: target_pos [U] int32 on the DEVICE (required); t has the bits ebn_ease_topk_f32 gives the same
+ *     (user, column) pair.
+ * One 256-thread workgroup per (user, split) walks ranges of ebn_ease_topk_range() columns: every thread keeps the sums of its
+ * own columns of the range in registers and reads, per present history entry, its 16 bytes of each of its groups of four columns
+ * of that row of B, several rows' loads in flight; the present entries of the history are staged once in LDS (256 at a time, in
+ * order).  Selection per wave in registers, the four lists merged by wave 0; the rank call evaluates the target column's chain
+ * first (one load per entry, folded in history order) and counts in the same walk.  n_splits: 0 =
+ * ebn_ease_topk_auto_splits(U, n_rows); clamped to the number of ranges and to 64; partial lists / counts in the workspace
+ * layouts of ebn_cv_topk_f32 / ebn_cv_target_rank_f32, merged / added by a second launch.  Results are bit-identical for every
+ * n_splits and from run to run.
+ * Any of n_rows / ldb / n_hists / n_hist_items / M / U outside [0, 2^31 - 1], X < 0, n_splits < 0, workspace_bytes < 0,
+ * ldb < n_rows, n_hist_items > 0 with n_hists = 0, cand_pos NULL with M != n_rows: EBN_ERR_BAD_ARG; then k outside [1, 64],
+ * X > 256 or n_rows > EBN_EASE_MAX_ITEMS: EBN_ERR_UNSUPPORTED; then U == 0: nothing to do (EBN_OK, no launch); then a NULL output,
+ * flags or target_pos: EBN_ERR_BAD_ARG; then n_rows == 0 or M == 0: empty outputs in one launch (-1 / -inf; rank 0, count 0,
+ * -inf, and flags[0] for a target position >= M); then a NULL B, hist_offsets with n_hists > 0 or hist_rows with
+ * n_hist_items > 0: EBN_ERR_BAD_ARG; then the workspace (NULL or too small: EBN_ERR_BAD_ARG; not 16-byte aligned: EBN_ERR_ALIGN).
+ * hist_weights, user_hist, cand_pos, window and exclude (then X counts as 0) may be NULL.                                         */
+/* The catalogue columns one pass of a workgroup covers.  Pure host query.                                                          */
+int64_t ebn_ease_topk_range(void);
+/* The number of column ranges n_splits = 0 stands for: 1 once the users alone give about 16 384 workgroups.  Pure host query, >= 1. */
+int ebn_ease_topk_auto_splits(int64_t n_users, int64_t n_rows);
+/* Bytes of workspace for n_splits >= 1, as ebn_cv_topk_workspace_bytes / ebn_cv_target_rank_workspace_bytes give them (a nominal
+ * 16 where none is needed; 0 for sizes outside the limits; n_positions: M when the rank call gets a cand_pos, else 0).  Pure host
+ * queries.                                                                                                                          */
+int64_t ebn_ease_topk_workspace_bytes(int64_t n_users, int32_t k, int32_t n_splits);
+int64_t ebn_ease_target_rank_workspace_bytes(int64_t n_users, int32_t n_splits, int64_t n_positions);
+int ebn_ease_topk_f32(const float* B, int64_t n_rows, int64_t ldb, const int32_t* hist_rows, const float* hist_weights,
+                      const int64_t* hist_offsets, int64_t n_hists, int64_t n_hist_items, const int32_t* user_hist,
+                      const int32_t* cand_pos, int64_t M, const int32_t* window, const int32_t* exclude, int32_t X, int32_t k,
+                      int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes,
+                      int64_t U, ebn_stream_t stream);
+int ebn_ease_target_rank_f32(const float* B, int64_t n_rows, int64_t ldb, const int32_t* hist_rows, const float* hist_weights,
+                             const int64_t* hist_offsets, int64_t n_hists, int64_t n_hist_items, const int32_t* user_hist,
+                             const int32_t* cand_pos, int64_t M, const int32_t* target_pos, const int32_t* window,
+                             const int32_t* exclude, int32_t X, int32_t n_splits, int32_t* out_rank, int32_t* out_count,
+                             float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U,
+                             ebn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
