@@ -9,7 +9,8 @@ from .covisit import (  # noqa: F401
 )
 from .ease import (EASE, ease_gram_host, ease_invert_host, ease_scores_host, ease_system_host, ease_target_rank_host, ease_topk_host,  # noqa: F401
                    ease_weights_host)
-from .knn import HistoryKNN, KNNIndex, knn_index_host, knn_neighbours_host, knn_scores_host  # noqa: F401
+from .knn import (HistoryKNN, KNNIndex, knn_index_host, knn_neighbours_host, knn_scores_host, knn_target_rank_host,  # noqa: F401
+                  knn_topk_host)
 from ._topn import TopN, dense_target_rank_host, dense_topk_host  # noqa: F401
 from .popularity import (  # noqa: F401
     ArticleFeatureBaseline, InviewEstimateBaseline, PopularityIndex, RecentPopularity, WindowCounts, lexicographic_scores,

@@ -5,7 +5,7 @@ counterpart of the neural models' ``recommend`` / ``rank_targets`` (ebrec/models
     ranks = cv.rank_targets(df_validation, history=df_history_validation)                # the clicked article among ALL articles
     rank_metrics(ranks.rank, ks=(5, 10), counts=ranks.count)                             # hit-rate@k, MRR, nDCG@k
 
-``TopN`` is the host scaffolding ``CoVisitation``, ``ImplicitALS``, ``ContentSimilarity`` and ``EASE`` share: the three call forms, the
+``TopN`` is the host scaffolding ``CoVisitation``, ``ImplicitALS``, ``ContentSimilarity``, ``EASE`` and ``HistoryKNN`` share: the three call forms, the
 candidate list, history exclusion, freshness windows, batching, the id mapping and the flags.  A class takes part by offering
 
     _topn_ids()                    -> the sorted article ids that name the catalogue rows
@@ -16,13 +16,19 @@ candidate list, history exclusion, freshness windows, batching, the id mapping a
         session.rank(hist_idx [b], target_pos [b], window, exclude, flags)                         -> (rank [b], count [b], score [b])
 
 with numpy arguments; the results are numpy on the host path and device tensors on the device path, ``flags`` [2] likewise.  Row
-b of a launch uses history ``hist_idx[b]`` (-1: none).  Co-visitation's session launches ``ebn_cv_topk_f32`` /
-``ebn_cv_target_rank_f32`` (covisit.py), EASE's ``ebn_ease_topk_f32`` / ``ebn_ease_target_rank_f32`` (ease.py); ``DenseSession`` below serves the two classes whose users are dense vectors -- ALS fold-in
+b of a launch uses history ``hist_idx[b]`` (-1: none).  A factory that names a ``history_keys`` parameter --
+``_topn_session(histories, history_keys=None)`` -- is also handed one key per history (``HistoryKNN``'s ``exclude_self`` matches
+them): the ``user_id`` the frames were joined on, the frame's own ``user_id`` column with a history per row, the caller's
+``history_keys=`` with the list form; the other classes are called as before and refuse ``history_keys=``.  Co-visitation's session launches ``ebn_cv_topk_f32`` /
+``ebn_cv_target_rank_f32`` (covisit.py), EASE's ``ebn_ease_topk_f32`` / ``ebn_ease_target_rank_f32`` (ease.py), history-kNN's
+``ebn_knn_topk_f32`` / ``ebn_knn_target_rank_f32`` (knn.py); ``DenseSession`` below serves the two classes whose users are dense vectors -- ALS fold-in
 rows, content-centroid profiles -- with the EXISTING ``ebn_topk_score_f32`` / ``ebn_topk_score_window_f32`` / ``ebn_target_rank_f32``
 (columns zero-padded to a multiple of 4), and with float64 numpy twins on the host.
 
-Out of scope: nearest-history top-N, the popularity baselines, re-rankers on baseline lists (DESIGN.md sections 31 and 35)."""
+Out of scope: nearest-history top-N, the popularity baselines, re-rankers on baseline lists (DESIGN.md sections 31, 35 and 36)."""
 from __future__ import annotations
+
+import inspect
 
 import numpy as np
 
@@ -205,6 +211,22 @@ def _users(behaviors, history):
     return RaggedLists(flat, off), np.where(users[at] == asked, at, -1).astype(np.int32), df, len(df)
 
 
+def _history_keys(model, history, frame, history_keys):
+    """(whether the model's session factory takes keys, one key per history of ``_users`` | None)"""
+    wants = "history_keys" in inspect.signature(model._topn_session).parameters
+    if history_keys is not None:
+        if not wants:
+            raise ValueError(f"{type(model).__name__} has no use for history_keys=")
+        if frame is not None:
+            raise ValueError("history_keys= belongs to the list form; the frames are joined on user_id")
+        return wants, history_keys
+    if not wants or frame is None:
+        return wants, None
+    if history is not None:
+        return wants, np.unique(_frame(history)[DEFAULT_USER_COL].to_numpy())  # the order of _users' histories
+    return wants, (frame[DEFAULT_USER_COL].to_numpy() if DEFAULT_USER_COL in frame.columns else None)
+
+
 def _candidates(model, candidate_ids):
     """(ids [M], rows [M] int32): ``None`` is every fitted article in row order; an unknown or a repeated id raises"""
     if candidate_ids is None:
@@ -247,13 +269,14 @@ def _raise_flags(flags):
 class _Plan:
     """what ``recommend`` and ``rank_targets`` share: users, candidates (by publish time under a window), windows, exclusion, session"""
 
-    def __init__(self, model, behaviors, history, candidate_ids, exclude_history, window, impression_times, batch_users):
+    def __init__(self, model, behaviors, history, candidate_ids, exclude_history, window, impression_times, batch_users, history_keys=None):
         if window is not None and not isinstance(window, Freshness):
             raise ValueError(f"window must be None or a Freshness(published, max_age, min_age), got {type(window).__name__}")
         if isinstance(batch_users, (bool, np.bool_)) or int(batch_users) != batch_users or int(batch_users) < 1:
             raise ValueError(f"batch_users must be a positive integer, got {batch_users!r}")
         self.batch = int(batch_users)
         self.histories, self.user_hist, self.frame, self.n = _users(behaviors, history)
+        wants_keys, keys = _history_keys(model, history, self.frame, history_keys)
         self.cand_ids, rows = _candidates(model, candidate_ids)
         self.win = None
         if window is not None:
@@ -274,7 +297,7 @@ class _Plan:
         if exclude_history:
             flat, off = _ragged_ids(self.histories)
             self.ex = _exclusion(model._topn_rows_of(flat), np.asarray(off, np.int64))
-        self.session = model._topn_session(self.histories)
+        self.session = model._topn_session(self.histories, history_keys=keys) if wants_keys else model._topn_session(self.histories)
         self.session.candidates(self.rows)
         if self.session.on_device:
             import torch
@@ -310,7 +333,7 @@ class TopN:
     """``recommend`` and ``rank_targets`` for a baseline (see the module docstring for what the class offers)."""
 
     def recommend(self, behaviors, candidate_ids=None, top_n=10, exclude_history=True, window=None, return_scores=False, fill_id=-1,
-                  batch_users=65536, *, history=None, impression_times=None):
+                  batch_users=65536, *, history=None, impression_times=None, history_keys=None):
         """ids [n, top_n]: each impression's ``top_n`` best of ``candidate_ids`` (``None``: every fitted article) by the model's score,
         best first, ties by position in ``candidate_ids``.  Call forms: ``recommend(behaviors, history=history_frame)`` joined on
         ``user_id``; ``recommend(behaviors)`` with ``article_id_fixed`` per row; ``recommend(histories)`` over a RaggedLists or lists
@@ -318,11 +341,12 @@ class TopN:
         ``window=Freshness(...)`` offers an impression only the candidates published inside its window (impression times from the
         frame's column or ``impression_times=``; equal scores then go to the older article).  A list left shorter than ``top_n`` --
         a user that cannot be scored gets an empty one -- is padded with ``fill_id`` (score -inf).  ``return_scores``: also the
-        float32 scores [n, top_n], numpy on the host path, a device tensor on the device path.  ``batch_users``: users per launch."""
+        float32 scores [n, top_n], numpy on the host path, a device tensor on the device path.  ``batch_users``: users per launch.
+        ``history_keys``: one key per history of the list form, for a class that matches them (``HistoryKNN``'s ``exclude_self``)."""
         if isinstance(top_n, (bool, np.bool_)) or int(top_n) != top_n or not 1 <= int(top_n) <= MAX_TOP_N:
             raise ValueError(f"top_n must be an integer in [1, {MAX_TOP_N}], got {top_n!r}")
         k = int(top_n)
-        plan = _Plan(self, behaviors, history, candidate_ids, exclude_history, window, impression_times, batch_users)
+        plan = _Plan(self, behaviors, history, candidate_ids, exclude_history, window, impression_times, batch_users, history_keys)
         pos_parts, score_parts = [], []
         for a in range(0, plan.n, plan.batch):
             imp = np.arange(a, min(a + plan.batch, plan.n), dtype=np.int64)
@@ -342,7 +366,7 @@ class TopN:
         return ids, _cat(score_parts, dev, np.zeros((0, k), np.float32))
 
     def rank_targets(self, behaviors, targets=None, candidate_ids=None, exclude_history=True, window=None, batch_users=65536, *,
-                     history=None, impression_times=None):
+                     history=None, impression_times=None, history_keys=None):
         """Where each impression's target article stands among ALL of ``candidate_ids`` by the model's score, under ``recommend``'s
         rules: a ``TargetRanks`` (impression, target_id, rank, count, score) with one entry per (impression, target) pair, as the
         neural ``rank_targets`` returns it; ``rank`` r <= k holds exactly when ``recommend(..., top_n=k)`` has the target at index
@@ -350,7 +374,7 @@ class TopN:
         target that is no candidate, is excluded, lies outside the window or has no score comes back with rank 0."""
         from ebrec.models.newsrec._recommend import TargetRanks
 
-        plan = _Plan(self, behaviors, history, candidate_ids, exclude_history, window, impression_times, batch_users)
+        plan = _Plan(self, behaviors, history, candidate_ids, exclude_history, window, impression_times, batch_users, history_keys)
         if targets is None:
             if plan.frame is None or DEFAULT_CLICKED_ARTICLES_COL not in plan.frame.columns:
                 raise ValueError(f"targets=None needs a behaviours frame with the column '{DEFAULT_CLICKED_ARTICLES_COL}'")

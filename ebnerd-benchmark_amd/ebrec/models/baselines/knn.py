@@ -25,7 +25,16 @@ Two paths, as in covisit.py.  With a visible GPU the neighbours come from ``ebn_
 ``ebn_knn_scores_f32`` (csrc/ebn_knn.hip; contract in include/ebnerd_hip.h): one launch over the histories, one over the items; the
 index is built by torch (composite int64 keys, sort, unique_consecutive, searchsorted) in blocks of at most ``max_keys`` keys.
 ``device=None`` or no GPU runs the numpy twins ``knn_index_host`` / ``knn_neighbours_host`` (float32 adds in item order: bit-equal to
-the kernel) / ``knn_scores_host`` (float64).  numpy / pandas on the host; torch is imported only on the device path."""
+the kernel) / ``knn_scores_host`` (float64).  numpy / pandas on the host; torch is imported only on the device path.
+
+TOP-N.  ``recommend`` / ``rank_targets`` (``TopN``, _topn.py) are the second outlet: each impression's best ``top_n`` of ALL fitted
+articles, and the full-catalogue rank of its clicked article, under history exclusion and freshness windows; ``exclude_self`` holds
+as in ``predict`` (frames joined on ``user_id`` match on that key, the list form takes ``history_keys=``).  Only an article some
+neighbour read has a score: a history without neighbours gets an empty list and rank 0.  The neighbour search runs ONCE per call;
+on the device the lists and ranks come from ``ebn_knn_topk_f32`` / ``ebn_knn_target_rank_f32`` (csrc/ebn_knn_topk.hip), which walk
+the neighbours' sets instead of searching them.  The numpy twins ``knn_topk_host`` / ``knn_target_rank_host`` add the sims in float32
+in neighbour-list order, vectorised over the rows of one neighbour, and are bit-equal to the kernels.  That chain is not the
+summation order of ``ebn_knn_scores_f32``: ``return_scores`` and ``predict`` agree to rounding, not in bits."""
 from __future__ import annotations
 
 import numpy as np
@@ -33,6 +42,7 @@ import numpy as np
 from ebrec.evaluation.device_metrics import RaggedLists, device_available
 from ebrec.utils._constants import DEFAULT_HISTORY_ARTICLE_ID_COL, DEFAULT_HISTORY_IMPRESSION_TIMESTAMP_COL, DEFAULT_USER_COL
 
+from ._topn import TopN
 from .content import ContentSimilarity, _list_histories, history_operands, join_frames
 from .covisit import _sequences
 from .popularity import _explode, _frame, _ragged_ids, _rows_of
@@ -41,6 +51,7 @@ MAX_K, MAX_SAMPLE = 512, 4096  # EBN_KNN_MAX_K / EBN_KNN_MAX_SAMPLE of include/e
 MAX_DIM = 2 ** 31 - 1
 SIMILARITIES = ("dot", "cosine")
 _CHUNK_PAIRS = 1 << 23  # (item, neighbour) pairs knn_scores_host materialises at a time
+MAX_TOP_K, MAX_EXCLUDE = 64, 256  # limits of the top-N kernels (include/ebnerd_hip.h)
 
 
 def _limits(k, sample_size):
@@ -182,6 +193,100 @@ def knn_scores_host(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, lis
     return out
 
 
+# ---- top-N over the whole catalogue: the numpy twins of ebn_knn_topk_f32 / ebn_knn_target_rank_f32 -------------------------------
+def knn_chains_host(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim) -> list:
+    """[(touched [n_rows] bool, score [n_rows] float32)] per neighbour row in the kernels' arithmetic: the slots in list order,
+    vectorised over the rows of one neighbour's set; the first touching neighbour assigns its sim, every later one adds it with one
+    float32 rounding; one float32 multiply by ``item_scale`` closes.  The part of both twins that depends on neither the candidates
+    nor the windows nor the exclusion lists (``chains=`` takes it, so that several calls share it)."""
+    s_indptr, s_items = np.asarray(s_indptr, np.int64).ravel(), np.asarray(s_items, np.int64).ravel()
+    n_seqs, nnz, n_rows = s_indptr.size - 1, s_items.size, int(n_rows)
+    nbr_seq, nbr_sim = np.asarray(nbr_seq, np.int64), np.asarray(nbr_sim, np.float32)
+    if nbr_seq.ndim != 2 or nbr_seq.shape != nbr_sim.shape or not 1 <= nbr_seq.shape[1] <= MAX_K:
+        raise ValueError(f"nbr_seq and nbr_sim must be [n_hists, k] with 1 <= k <= {MAX_K}")
+    scale = None if item_scale is None else np.asarray(item_scale, np.float32).ravel()
+    out = []
+    with np.errstate(all="ignore"):
+        for seqs, sims in zip(nbr_seq, nbr_sim):
+            touched, acc = np.zeros(n_rows, bool), np.zeros(n_rows, np.float32)
+            for s, sim in zip(seqs.tolist(), sims):
+                if not 0 <= s < n_seqs:
+                    continue
+                a, b = (min(max(int(v), 0), nnz) for v in (s_indptr[s], s_indptr[s + 1]))
+                c = s_items[a:b]
+                c = c[(c >= 0) & (c < n_rows)]
+                acc[c] = np.where(touched[c], acc[c] + sim, sim)  # float32 + float32: one rounding
+                touched[c] = True
+            out.append((touched, acc if scale is None else acc * scale))
+    return out
+
+
+def _topn_walk_host(chains, n_rows, user_hist, n_users, cand_pos, M, window, exclude):
+    """per user: (admissible rows, their positions, the float32 scores of all rows), and the two flags at the end"""
+    n_hists = len(chains)
+    pos_of = np.arange(n_rows, dtype=np.int64) if cand_pos is None else np.asarray(cand_pos, np.int64).ravel()
+    if pos_of.size != n_rows or (cand_pos is None and M != n_rows):
+        raise ValueError(f"cand_pos must hold one position per catalogue row ({n_rows}); without it M == n_rows")
+    flags = np.zeros(2, np.int32)
+    for u in range(int(n_users)):
+        h = u if user_hist is None else int(user_hist[u])
+        touched, score = np.zeros(n_rows, bool), np.zeros(n_rows, np.float32)
+        if 0 <= h < n_hists:
+            touched, score = chains[h]
+        lo, hi = 0, int(M)
+        if window is not None:
+            lo, hi = max(int(window[u][0]), 0), min(int(window[u][1]), int(M))
+            if lo >= hi:
+                lo = hi = 0
+        if (touched & (pos_of >= M)).any():
+            flags[0] = 1
+        adm = touched & (pos_of >= lo) & (pos_of < hi)
+        if exclude is not None:
+            ex = np.asarray(exclude[u], np.int64).ravel()
+            adm[ex[(ex >= 0) & (ex < n_rows)]] = False
+        if (adm & np.isnan(score)).any():
+            flags[1] = 1
+        adm &= ~np.isnan(score)
+        rows = np.flatnonzero(adm)
+        yield u, rows, pos_of[rows], score, flags
+
+
+def knn_topk_host(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, user_hist, n_users, cand_pos, M, window, exclude, k, chains=None):
+    """numpy twin of ebn_knn_topk_f32, bit-equal to it -> (pos [U, k] int32, score [U, k] float32, flags [2] int32)"""
+    if not 1 <= int(k) <= MAX_TOP_K:
+        raise ValueError(f"k must lie in [1, {MAX_TOP_K}], got {k}")
+    if chains is None:
+        chains = knn_chains_host(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim)
+    out_pos, out_score = np.full((int(n_users), int(k)), -1, np.int32), np.full((int(n_users), int(k)), -np.inf, np.float32)
+    flags = np.zeros(2, np.int32)
+    for u, rows, pos, score, flags in _topn_walk_host(chains, int(n_rows), user_hist, n_users, cand_pos, M, window, exclude):
+        s = score[rows]
+        best = np.lexsort((pos, -s))[:int(k)]  # score descending, then position ascending
+        out_pos[u, :best.size], out_score[u, :best.size] = pos[best], s[best]
+    return out_pos, out_score, flags
+
+
+def knn_target_rank_host(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, user_hist, n_users, cand_pos, M, target_pos, window, exclude,
+                         chains=None):
+    """numpy twin of ebn_knn_target_rank_f32 -> (rank [U] int32, count [U] int32, score [U] float32, flags [2] int32)"""
+    if chains is None:
+        chains = knn_chains_host(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim)
+    target_pos = np.asarray(target_pos, np.int64).ravel()
+    U = int(n_users)
+    rank, count, t_out = np.zeros(U, np.int32), np.zeros(U, np.int32), np.full(U, -np.inf, np.float32)
+    flags, oob_target = np.zeros(2, np.int32), bool((target_pos[:U] >= M).any())
+    for u, rows, pos, score, flags in _topn_walk_host(chains, int(n_rows), user_hist, n_users, cand_pos, M, window, exclude):
+        count[u] = rows.size
+        at = np.flatnonzero(pos == target_pos[u]) if 0 <= target_pos[u] < M else np.zeros(0, np.int64)
+        if at.size:
+            s, t = score[rows], score[rows[at[0]]]
+            rank[u] = 1 + int(((s > t) | ((s == t) & (pos < target_pos[u]))).sum())
+            t_out[u] = t
+    if oob_target:
+        flags[0] = 1
+    return rank, count, t_out, flags
+
+
 # ---- the index -----------------------------------------------------------------------------------------------------------------
 class KNNIndex:
     """``article_ids`` (sorted, numpy) name the rows; ``p_indptr`` int64 / ``p_seqs`` int32 are the postings, ``s_indptr`` int64 /
@@ -284,8 +389,136 @@ def scores_call(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, list_hi
     return scores
 
 
+def _topn_operands(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, user_hist, cand_pos, M):
+    from ebrec import _hip
+
+    n_rows = int(n_rows)
+    M = n_rows if cand_pos is None else int(M)
+    return (_hip.ptr(s_indptr), _hip.ptr(s_items), s_indptr.numel() - 1, s_items.numel(), n_rows, _hip.ptr(item_scale), _hip.ptr(nbr_seq),
+            _hip.ptr(nbr_sim), nbr_seq.shape[0], nbr_seq.shape[1], _hip.ptr(user_hist), _hip.ptr(cand_pos), M)
+
+
+def _check_topn_args(U, nbr_seq, nbr_sim, window, exclude, target_pos=None):
+    import torch
+
+    if nbr_seq.dim() != 2 or nbr_seq.shape != nbr_sim.shape or nbr_seq.dtype != torch.int32 or nbr_sim.dtype != torch.float32 or \
+            not (nbr_seq.is_contiguous() and nbr_sim.is_contiguous()):
+        raise ValueError("nbr_seq int32 and nbr_sim float32 must be contiguous [n_hists, k] tensors")
+    for name, t, shape in (("window", window, (U, 2)), ("exclude", exclude, None), ("target_pos", target_pos, (U,))):
+        if t is None:
+            continue
+        if t.dtype != torch.int32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape) or \
+                (shape is None and (t.dim() != 2 or t.shape[0] != U)):
+            raise ValueError(f"{name} must be a contiguous int32 tensor with one row per user ({U}), got {tuple(t.shape)} {t.dtype}")
+
+
+def topk_call(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, user_hist, n_users, cand_pos, M, window, exclude, k, flags,
+              n_splits: int = 0):
+    """One ebn_knn_topk_f32 launch over device tensors (``item_scale`` / ``user_hist`` / ``cand_pos`` / ``window`` [U, 2] /
+    ``exclude`` [U, X] may be None) -> (pos [U, k] int32, score [U, k] float32); ``flags`` [2] int32 accumulates."""
+    import torch
+
+    from ebrec import _hip
+
+    U, dev = int(n_users), s_indptr.device
+    _check_topn_args(U, nbr_seq, nbr_sim, window, exclude)
+    ops = _topn_operands(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, user_hist, cand_pos, M)
+    pos = torch.empty(U, k, dtype=torch.int32, device=dev)
+    score = torch.empty(U, k, dtype=torch.float32, device=dev)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_knn_topk_auto_splits(U, int(n_rows)))
+    ws = torch.empty(max(int(lib.ebn_knn_topk_workspace_bytes(U, k, max(splits, 1))), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("ebn_knn_topk_f32", *ops, _hip.ptr(window), _hip.ptr(exclude), 0 if exclude is None else exclude.shape[1], int(k), splits,
+                  _hip.ptr(pos), _hip.ptr(score), _hip.ptr(flags), _hip.ptr(ws), ws.numel(), U, _hip.stream_handle())
+    return pos, score
+
+
+def target_rank_call(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, user_hist, n_users, cand_pos, M, target_pos, window, exclude,
+                     flags, n_splits: int = 0):
+    """One ebn_knn_target_rank_f32 launch over device tensors: ``target_pos`` [U] int32 candidate positions (< 0: none) -> (rank [U]
+    int32: 1-based place in ``topk_call``'s order, 0 = not ranked; count [U] int32: the user's admissible rows; score [U] float32:
+    the target's score, -inf where rank is 0); ``flags`` accumulates."""
+    import torch
+
+    from ebrec import _hip
+
+    U, dev = int(n_users), s_indptr.device
+    _check_topn_args(U, nbr_seq, nbr_sim, window, exclude, target_pos)
+    ops = _topn_operands(s_indptr, s_items, n_rows, item_scale, nbr_seq, nbr_sim, user_hist, cand_pos, M)
+    rank = torch.empty(U, dtype=torch.int32, device=dev)
+    count = torch.empty(U, dtype=torch.int32, device=dev)
+    score = torch.empty(U, dtype=torch.float32, device=dev)
+    lib = _hip.lib()
+    splits = n_splits if n_splits > 0 else int(lib.ebn_knn_topk_auto_splits(U, int(n_rows)))
+    ws = torch.empty(max(int(lib.ebn_knn_target_rank_workspace_bytes(U, max(splits, 1), 0 if cand_pos is None else int(M))), 16),
+                     dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("ebn_knn_target_rank_f32", *ops, _hip.ptr(target_pos), _hip.ptr(window), _hip.ptr(exclude),
+                  0 if exclude is None else exclude.shape[1], splits, _hip.ptr(rank), _hip.ptr(count), _hip.ptr(score), _hip.ptr(flags),
+                  _hip.ptr(ws), ws.numel(), U, _hip.stream_handle())
+    return rank, count, score
+
+
+class KnnSession:
+    """what ``TopN`` drives (see _topn.py): the histories of one ``recommend`` / ``rank_targets`` call.  The neighbour search has run
+    ONCE over them (``nbr_seq`` / ``nbr_sim`` [n_hists, k]: device tensors -> the two kernels, numpy arrays -> the float32 twins);
+    every batch launch passes ``user_hist = hist_idx``."""
+
+    def __init__(self, index: "KNNIndex", nbr_seq, nbr_sim):
+        self.on_device = not isinstance(nbr_seq, np.ndarray)
+        self.n_rows, self.seq, self.sim = index.n_rows, nbr_seq, nbr_sim
+        self.cand_pos, self.M, self.device = None, index.n_rows, None
+        if self.on_device:
+            self.device = nbr_seq.device
+            self.sets = (index.s_indptr, index.s_items, index.n_rows, index.item_scale)
+        else:
+            _, _, s_indptr, s_items, _, item_scale = index.host()
+            self.sets = (s_indptr, s_items, index.n_rows, item_scale)
+            self.chains = knn_chains_host(*self.sets, nbr_seq, nbr_sim)  # once for every batch of the call
+
+    def candidates(self, cand_rows):
+        """position -> row becomes the kernels' row -> position (-1: no candidate); the identity is passed as None"""
+        rows = np.asarray(cand_rows, np.int64)
+        self.M = rows.size
+        if rows.size == self.n_rows and np.array_equal(rows, np.arange(self.n_rows)):
+            self.cand_pos = None
+            return
+        pos = np.full(self.n_rows, -1, np.int32)
+        pos[rows] = np.arange(rows.size, dtype=np.int32)
+        self.cand_pos = pos
+        if self.on_device:
+            import torch
+
+            self.cand_pos = torch.from_numpy(pos).to(self.device)
+
+    def _up(self, a):
+        import torch
+
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    def topk(self, hist_idx, window, exclude, k, flags):
+        U = len(hist_idx)
+        if not self.on_device:
+            pos, score, f = knn_topk_host(*self.sets, self.seq, self.sim, hist_idx, U, self.cand_pos, self.M, window, exclude, k, self.chains)
+            flags |= f
+            return pos, score
+        return topk_call(*self.sets, self.seq, self.sim, self._up(hist_idx), U, self.cand_pos, self.M, self._up(window), self._up(exclude), k,
+                         flags)
+
+    def rank(self, hist_idx, target_pos, window, exclude, flags):
+        U = len(hist_idx)
+        if not self.on_device:
+            rank, count, score, f = knn_target_rank_host(*self.sets, self.seq, self.sim, hist_idx, U, self.cand_pos, self.M, target_pos, window,
+                                                         exclude, self.chains)
+            flags |= f
+            return rank, count, score
+        return target_rank_call(*self.sets, self.seq, self.sim, self._up(hist_idx), U, self.cand_pos, self.M, self._up(target_pos),
+                                self._up(window), self._up(exclude), flags)
+
+
 # ---- the class -----------------------------------------------------------------------------------------------------------------
-class HistoryKNN:
+class HistoryKNN(TopN):
     """Sequence-neighbourhood scores.  ``k``: the neighbours of a history (1 to 512, at most ``sample_size``); ``sample_size``: the most
     recent sequences sharing an article with it that are compared at all (1 to 4096); ``similarity``: "dot" or "cosine";
     ``history_weights`` / ``lambda_factor`` / ``history_size`` / ``fill``: as in ``ContentSimilarity``; ``idf``: weigh an article's
@@ -407,6 +640,20 @@ class HistoryKNN:
                                    self.sample_size, self.k)
         p_indptr, p_seqs, _, _, seq_scale, _ = ix.host()
         return knn_neighbours_host(p_indptr, p_seqs, ix.n_seqs, seq_scale, h_rows, w, h_off, hist_self, self.sample_size, self.k)
+
+    # -- recommend / rank_targets (TopN, _topn.py): ebn_knn_topk_f32 / ebn_knn_target_rank_f32 over the sets.  Only an article some
+    # neighbour read has a score; a history without neighbours gets an empty list and rank 0
+    def _topn_ids(self):
+        return self._fitted().article_ids
+
+    def _topn_rows_of(self, ids):
+        return self.rows_of(ids)
+
+    def _topn_session(self, histories, history_keys=None):
+        ix = self._fitted()
+        h_rows, h_off, w = self._histories(histories)
+        seq, sim = self._neighbours(h_rows, h_off, w, self._self_of(history_keys, h_off.size - 1))
+        return KnnSession(ix, seq, sim)
 
     # -- public
     def neighbours(self, histories, history_keys=None):

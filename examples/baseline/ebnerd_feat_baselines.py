@@ -20,7 +20,7 @@ baseline and writes one zipped submission file per baseline into --dump_dir:
   * ease (with --ease): the item-to-item ridge regression EASE^R (``EASE``: regularization --ease_reg, 500 by default, the 16384
     most-clicked articles), fitted on train/history.parquet and scored against each user's validation/history.parquet.
 
---topn K adds, for each of covisit, als and ease that is selected, the full-catalogue view (``recommend`` / ``rank_targets``): where the
+--topn K adds, for each of covisit, als, knn and ease that is selected, the full-catalogue view (``recommend`` / ``rank_targets``): where the
 clicked article stands among ALL fitted articles under the user's validation history (hit-rate@K, MRR, nDCG@K,
 ``ebrec.evaluation.rank_metrics``) and what the K-lists look like beyond accuracy: coverage of the fitted catalogue and novelty
 (mean -log2 of an article's share of the train-history clicks, relative to the most clicked one).
@@ -71,7 +71,7 @@ def get_args(argv=None):
     ap.add_argument("--ease", action="store_true", help="add the EASE baseline (fit on the train history)")
     ap.add_argument("--ease_reg", type=float, default=500.0, metavar="R", help="EASE's ridge regularization")
     ap.add_argument("--topn", type=int, default=0, metavar="K", help="also rank the clicked articles among ALL fitted articles and judge the "
-                    "top-K lists (covisit / als / ease), 1 to 64")
+                    "top-K lists (covisit / als / knn / ease), 1 to 64")
     ap.add_argument("--blend", action="store_true", help="add a cross-fitted blend of every baseline of the run (5 folds by user)")
     ap.add_argument("--blend_transform", default="zscore", choices=["raw", "zscore", "minmax", "rank", "rrf"],
                     help="per-list transform of every column before the blend")
@@ -158,6 +158,7 @@ def main(argv=None):
             df_knn_history = pd.read_parquet(PATH / args.datasplit / "validation" / "history.parquet")
             print(f"knn: {knn.index.n_seqs} sequences of {knn.index.n_rows} articles, k 100 of the 1000 most recent, cosine, linear weights")
             baselines["knn_prediction_scores"] = lambda frame: knn.predict(frame, history=df_knn_history)
+            topn["knn"] = (knn, knn.index.article_ids, df_knn_history)
         else:
             skipped["knn_prediction_scores"] = f"history.parquet has no column '{DEFAULT_HISTORY_ARTICLE_ID_COL}'"
     if args.ease:

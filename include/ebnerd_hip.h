@@ -1674,6 +1674,64 @@ int ebn_knn_scores_f32(const int64_t* s_indptr, const int32_t* s_items, int64_t 
                        const int32_t* list_hist, const int32_t* cand_rows, const int64_t* cand_offsets, int64_t n_lists,
                        int64_t n_cand_items, float* scores, ebn_stream_t stream);
 
+/* ---- history-kNN top-N lists and clicked-article ranks over the whole catalogue (csrc/ebn_knn_topk.hip, ebn_knn_tile.h; the
+ * plain-Python brute force of tests/knn_topn_cases.py is the yardstick): what ebn_cv_topk_f32 and ebn_cv_target_rank_f32 are to the
+ * co-visitation matrix, for the score of ebn_knn_scores_f32 -----------------------------------------------------------------------
+ * Everything not said here is ebn_cv_topk_f32's / ebn_cv_target_rank_f32's: user_hist, cand_pos and M, window [U, 2] and its
+ * clamping, exclude [U, X] matching by catalogue row, the total order, flags [2] only ever SET, target_pos, the rank / count / score
+ * outputs, n_splits and the workspace layouts, all argument checks on the host before anything is launched.
+ * SETS: s_indptr [n_seqs + 1] int64 / s_items [nnz_s] int32 of the fitted index, as ebn_knn_scores_f32 takes them: the rows of a set
+ * are distinct and ASCENDING.  Every extent read from s_indptr is clamped to [0, nnz_s] (end < begin: empty); every row read from
+ * s_items is checked against the rows of the tile in hand before it addresses anything.  item_scale [n_rows] fp32 or NULL.
+ * NEIGHBOURS: nbr_seq / nbr_sim [n_hists, k_nbr] as ebn_knn_neighbours_f32 leaves them, 1 <= k_nbr <= EBN_KNN_MAX_K; user u of U
+ * uses row user_hist ? user_hist[u] : u, an index outside [0, n_hists) is a user without neighbours.  A sequence id outside
+ * [0, n_seqs) is an ABSENT neighbour.
+ * SCORE: row c is TOUCHED by user u when the set of at least one present neighbour holds it.  The neighbour slots are walked in
+ * list order j = 0 .. k_nbr - 1: the first touching neighbour assigns acc = sim_j, every later one does acc = acc + sim_j, each add
+ * rounding once to fp32; then score = item_scale ? acc * item_scale[c] (one rounding) : acc.  A sequence listed twice counts
+ * twice.  No floating-point atomics.  A score's bits depend on that user's neighbour row and the sets only: not on U, M, n_splits,
+ * the run or the other users of the launch.
+ * ADMISSIBLE: row c for user u when it is touched, cand_pos[c] lies in [0, M) and in u's clamped window, c is not in exclude[u, :]
+ * and the score is not NaN.  A NaN score of a row that is admissible otherwise sets flags[1]; a touched row with cand_pos[c] >= M
+ * sets flags[0].  An untouched row never enters a list; a touched row with score 0 or below does.
+ *   ebn_knn_topk_f32: out_pos [U, k] / out_score [U, k]: each user's best k admissible rows as (position, score), score descending,
+ *     then position ascending; -1 / -inf in the empty trailing slots.  1 <= k <= 64.
+ *   ebn_knn_target_rank_f32: target_pos [U] int32 on the DEVICE (required); out_rank / out_count / out_score as
+ *     ebn_target_rank_f32 defines them over this admissible set; rank 0 (score -inf) when there is no target (< 0; >= M also sets
+ *     flags[0]), the position belongs to no row, or the target's row is untouched or not admissible.  The target's score has the
+ *     bits ebn_knn_topk_f32 gives the same (user, row) pair.
+ * One 256-thread workgroup per (user, split) stages the neighbour row in LDS once and walks ranges of ebn_knn_topk_range() catalogue
+ * rows; every wave owns a quarter of the range as a private fp32 tile with two bits per row, cuts all sets to it with one lane per
+ * neighbour and applies the neighbours with a segment in list order: no workgroup barrier inside the walk (42 KiB of LDS).
+ * Results are bit-identical for every n_splits and from run to run.
+ * Any of n_seqs / nnz_s / n_rows / n_hists / M / U outside [0, 2^31 - 1], X < 0, n_splits < 0, workspace_bytes < 0, k_nbr < 1,
+ * cand_pos NULL with M != n_rows: EBN_ERR_BAD_ARG; then k outside [1, 64], X > 256 or k_nbr > EBN_KNN_MAX_K: EBN_ERR_UNSUPPORTED;
+ * then U == 0: nothing to do (EBN_OK, no launch); then a NULL output, flags or target_pos: EBN_ERR_BAD_ARG; then n_rows == 0,
+ * n_seqs == 0, nnz_s == 0 or M == 0: empty outputs in one launch (-1 / -inf; rank 0, count 0, -inf, and flags[0] for a target
+ * position >= M); then a NULL s_indptr / s_items, or nbr_seq / nbr_sim with n_hists > 0: EBN_ERR_BAD_ARG; then the workspace
+ * (too small or NULL: EBN_ERR_BAD_ARG; not 16-byte aligned: EBN_ERR_ALIGN).  item_scale, user_hist, cand_pos, window and exclude
+ * (then X counts as 0) may be NULL.                                                                                                */
+/* The catalogue rows one range covers (four wave tiles).  Pure host query.                                                          */
+int64_t ebn_knn_topk_range(void);
+/* The number of row ranges n_splits = 0 stands for: 1 once the users alone give about 2 048 workgroups.  Pure host query, >= 1.   */
+int ebn_knn_topk_auto_splits(int64_t n_users, int64_t n_rows);
+/* Bytes of workspace for n_splits >= 1, as ebn_cv_topk_workspace_bytes / ebn_cv_target_rank_workspace_bytes give them (a nominal
+ * 16 where none is needed; 0 for sizes outside the limits; n_positions: M when the rank call gets a cand_pos, else 0).  Pure host
+ * queries.                                                                                                                          */
+int64_t ebn_knn_topk_workspace_bytes(int64_t n_users, int32_t k, int32_t n_splits);
+int64_t ebn_knn_target_rank_workspace_bytes(int64_t n_users, int32_t n_splits, int64_t n_positions);
+int ebn_knn_topk_f32(const int64_t* s_indptr, const int32_t* s_items, int64_t n_seqs, int64_t nnz_s, int64_t n_rows,
+                     const float* item_scale, const int32_t* nbr_seq, const float* nbr_sim, int64_t n_hists, int32_t k_nbr,
+                     const int32_t* user_hist, const int32_t* cand_pos, int64_t M, const int32_t* window, const int32_t* exclude,
+                     int32_t X, int32_t k, int32_t n_splits, int32_t* out_pos, float* out_score, int32_t* flags, void* workspace,
+                     int64_t workspace_bytes, int64_t U, ebn_stream_t stream);
+int ebn_knn_target_rank_f32(const int64_t* s_indptr, const int32_t* s_items, int64_t n_seqs, int64_t nnz_s, int64_t n_rows,
+                            const float* item_scale, const int32_t* nbr_seq, const float* nbr_sim, int64_t n_hists, int32_t k_nbr,
+                            const int32_t* user_hist, const int32_t* cand_pos, int64_t M, const int32_t* target_pos,
+                            const int32_t* window, const int32_t* exclude, int32_t X, int32_t n_splits, int32_t* out_rank,
+                            int32_t* out_count, float* out_score, int32_t* flags, void* workspace, int64_t workspace_bytes, int64_t U,
+                            ebn_stream_t stream);
+
 /* ---- EASE^R baseline (Steck, "Embarrassingly Shallow Autoencoders for Sparse Data", WWW 2019): the item-to-item ridge regression in
  * closed form (the reference has no such baseline; the float64 brute force of tests/ease_cases.py is the yardstick; host layer:
  * ebrec/models/baselines/ease.py; kernels: csrc/ebn_ease.hip) ---------------------------------------------------------------------
